@@ -14,7 +14,14 @@ under the compute: backend/tools/chunk_parallel.py), are inpainted there and ret
 `value` = N x 50 x K frames / max-over-ranks time.  The replica rate (every rank on its own resident
 chunk, nothing exchanged) is reported beside it as `replicas`.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = one timed step).
+With N > 1 a plain run still times the replicas leg before the exchange: it is the rate the line
+falls back to when the exchange fails.
+--dump-outputs DIR: after the timed steps, what the last step handed back (the inpainted frames) is written
+as float32 .npy under DIR (dump_outputs; the inputs are seeded, so two builds compare output for output).
+--full: every other leg below (and, N > 1, the selftest of the exchanged bytes) after the timed steps.
+
+Extra objects in the line (--full):
   roofline     -- the dominant kernel symbol (the gather-GEMM instantiation with the largest total time:
                   gather_gemm_f32_v3<128, 64, 2, 2, 0>, the 3x3 / 1x1 convs and QK^T as implicit GEMMs, 83 % of
                   the GPU time), algorithmic FLOPs / HIP-event time on the launch stream against the 157.3 TFLOP/s
@@ -66,6 +73,26 @@ def make_chunk_on_device(L, H, W, box, seed, device):
     d = torch.from_numpy(base).to(device)
     reps = [torch.roll(d, shifts=(3 * k, 5 * k), dims=(1, 2)) for k in range((L + base.shape[0] - 1) // base.shape[0])]
     return torch.cat(reps, 0)[:L].contiguous()
+
+
+DUMP_BOX_ELEMS = 12 << 20          # float32 elements per dumped array: 48 MiB + 8 MiB in all
+DUMP_FRAME_ELEMS = 2 << 20
+
+
+def dump_outputs(path, frames, box):
+    """--dump-outputs: the frames the timed path handed back after its last step (uint8 [..., H, W, 3] on the device; the clip is
+    seeded, so the same arguments give the same inputs) as float32 .npy under `path`:
+      inpainted_box.npy -- the pixels inside the mask's bounding box `box` = (ymin, ymax, xmin, xmax), in order when they fit
+                           DUMP_BOX_ELEMS, else a fixed seeded sample of them (flat, sorted positions);
+      frames_sample.npy -- a fixed seeded sample of every pixel of the frames (outside the mask they come back as they went in)."""
+    os.makedirs(path, exist_ok=True)
+    y0, y1, x0, x1 = box
+    for name, t, cap, seed in (("inpainted_box", frames[..., y0:y1, x0:x1, :], DUMP_BOX_ELEMS, 11),
+                               ("frames_sample", frames, DUMP_FRAME_ELEMS, 12)):
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(seed).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32))
 
 
 def cpu_model_name():
@@ -260,13 +287,23 @@ def main():
     ap.add_argument("--precision", default=None, choices=["f32", "split", "split-format", "f16"],
                     help="arithmetic of the contractions in the timed region (default: exact fp32; BASELINE.json's config 5 "
                          "is --res 4k --precision f16)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every informational leg (single_lane / roofline / breakdowns, cpu_baseline, "
+                         "pcie_inclusive, the reduced-precision modes, full_work, configs; N > 1: selftest, configs_multi); the --no-* "
+                         "options above switch single legs off again.  Without it the run times the headline and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as float32 .npy files under DIR (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_selftest = args.no_multi_configs = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1 and "RANK" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become `python -m torch.distributed.run --nproc-per-node N bench.py ...` (one
+        # `python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nproc-per-node N bench.py ...` (one
         # process per GPU; rank 0 still prints the ONE JSON line).  HSA_ENABLE_IPC_MODE_LEGACY=0 is already in the environment (above).
         import socket
 
@@ -276,7 +313,9 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess
+
+        raise SystemExit(subprocess.call(cmd))       # a fresh child process, not an exec of this one; its exit status is the run's
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch one rank per GPU (python bench.py --gpus N does it itself)")
     if not torch.cuda.is_available():
@@ -350,6 +389,8 @@ def main():
         # the timed region carries no events: with two lanes (vsr_sttn_set_lanes, the default) launches of the two streams overlap,
         # so per-launch durations are taken in a single-lane pass afterwards (roofline_leg) and the per-op breakdown after that
         elapsed = timed(lambda: [step() for _ in range(args.steps)])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, work, box)
     else:
         # N > 1: the north-star data path.  A step = one round of N chunks: all resident in rank 0's HBM, the rows between the
         # first and the last strip of chunk k go to rank k (RCCL send / recv over xGMI), are inpainted there in place and come
@@ -424,6 +465,8 @@ def main():
             sys.stdout.flush()
             os._exit(0)
         if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, torch.stack(dsts), (box[0] - y_lo, box[1] - y_lo, box[2], box[3]))
             checksum = int(sum(int(d[::7, ::5, ::11].sum().item()) for d in dsts))
             replicas["scatter_gather_result_checksum"] = checksum
         if not args.no_selftest:
@@ -483,29 +526,31 @@ def main():
     # ---- roofline leg: K steps of the same resident chunk on ONE lane, HIP events on the launch stream around every launch of the
     # dominant kernel symbol (one record pair per launch, ~410 of the ~1300 launches of a chunk, read back once per chunk).  With
     # two lanes a launch's event-to-event time contains the other lane's work, and rocprofv3's per-kernel durations do too
-    # (profiles/: the kernel-trace summary that agrees with this leg is the one of `bench.py --lanes 1`).
-    eng.set_lanes(1)
-    step()
-    torch.cuda.synchronize()
-    eng.timing(2)
-    eng.timing_reset()
-    torch.cuda.synchronize()
-    t_leg = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    t_leg = time.perf_counter() - t_leg
-    eng.timing(False)
+    # (profiles/: the kernel-trace summary that agrees with this leg is the one of `bench.py --full --lanes 1`).
+    # It and everything after it up to eng.close() run with --full only.
     out["lanes"] = args.lanes
-    out["single_lane"] = {"value": round(args.steps * L / t_leg, 3), "unit": "frames/s (this rank, resident chunk)",
-                          "ms_per_step": round(t_leg / args.steps * 1e3, 3),
-                          "note": "the same step with every op on one stream (vsr_sttn_set_lanes(1)), dominant-kernel launches bracketed by "
-                                  "HIP events: the pass `roofline` is measured on"}
+    if args.full:
+        eng.set_lanes(1)
+        step()
+        torch.cuda.synchronize()
+        eng.timing(2)
+        eng.timing_reset()
+        torch.cuda.synchronize()
+        t_leg = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        t_leg = time.perf_counter() - t_leg
+        eng.timing(False)
+        out["single_lane"] = {"value": round(args.steps * L / t_leg, 3), "unit": "frames/s (this rank, resident chunk)",
+                              "ms_per_step": round(t_leg / args.steps * 1e3, 3),
+                              "note": "the same step with every op on one stream (vsr_sttn_set_lanes(1)), dominant-kernel launches bracketed by "
+                                      "HIP events: the pass `roofline` is measured on"}
     if replicas is not None:
         out["replicas"] = replicas
     if world > 1:          # the CPU baseline and the informational legs belong to the N = 1 line only
         args.no_cpu_baseline, args.no_split_half, args.e2e_chunks, args.no_full_work, args.no_configs = True, True, 0, True, True
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel from the HIP events of the timed region
         # dominant kernel symbol = the gather-GEMM instantiation with the largest total time; every
         # launch of that symbol is counted (same population as rocprofv3 --stats's per-kernel row)

@@ -1,6 +1,6 @@
 mkdir -p gpurun_out/abt; export TMPDIR=/tmp
 (timeout 600 python -m pytest tests -m gpu -q --tb=short -x -k "split_format or fp16 or split_half" 2>&1 | tail -4)
-B="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-split-half --e2e-chunks 0"
+B="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-split-half --e2e-chunks 0"
 run() { name=$1; shift; env "$@" $B > gpurun_out/abt/$name.log 2>&1; python - gpurun_out/abt/$name.log $name <<'PY'
 import json,sys
 ok=False

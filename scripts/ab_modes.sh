@@ -1,6 +1,6 @@
 # per-op timing of the three arithmetic modes on the bench workload (timed region only)
 mkdir -p gpurun_out/abm; export TMPDIR=/tmp
-B="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-split-half --e2e-chunks 0"
+B="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-split-half --e2e-chunks 0"
 run() { name=$1; shift; env "$@" $B > gpurun_out/abm/$name.log 2>&1; python - gpurun_out/abm/$name.log $name <<'PY'
 import json,sys
 ok=False

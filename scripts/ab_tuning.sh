@@ -1,6 +1,6 @@
 # interleaved A/B inside split-half mode (tile shapes)
 mkdir -p gpurun_out/ab; export TMPDIR=/tmp
-B="python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-split-half"
+B="python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-split-half"
 run() { name=$1; shift; env "$@" $B > gpurun_out/ab/$name.log 2>&1; python - gpurun_out/ab/$name.log $name <<'PY'
 import json,sys
 ok=False

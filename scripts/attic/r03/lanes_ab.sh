@@ -3,7 +3,7 @@
 OUT=gpurun_out/r03_lanes; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_sttn.py -m gpu -x -q -k lanes 2>&1 | tail -4
 for l in 2 3 4; do
-  python bench.py --lanes $l --no-cpu-baseline --e2e-chunks 0 > $OUT/bench_lanes$l.log 2>&1
+  python bench.py --full --lanes $l --no-cpu-baseline --e2e-chunks 0 > $OUT/bench_lanes$l.log 2>&1
   python - <<PY
 import json
 l=[x for x in open('gpurun_out/r03_lanes/bench_lanes$l.log') if x.startswith('{"metric"')]

@@ -11,7 +11,7 @@ for kind in ["fetch","tcc"]:
     print('qk grouped order, 8 queues', kind, d.groupby('Counter_Name').Counter_Value.mean().to_dict())
 PY
 timeout 600 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_sttn.py -m gpu -x -q 2>&1 | tail -3
-for s in 0 1; do VSR_GG_SWIZZLE=$s python bench.py --no-cpu-baseline --e2e-chunks 0 --no-split-half > $OUT/bench_swz$s.log 2>&1; python - <<PY
+for s in 0 1; do VSR_GG_SWIZZLE=$s python bench.py --full --no-cpu-baseline --e2e-chunks 0 --no-split-half > $OUT/bench_swz$s.log 2>&1; python - <<PY
 import json
 l=[x for x in open('gpurun_out/r03_swz/bench_swz$s.log') if x.startswith('{"metric"')][0]
 d=json.loads(l)

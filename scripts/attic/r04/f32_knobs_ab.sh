@@ -2,7 +2,7 @@
 # exact-fp32 bench, interleaved A/B of the tile knobs after the round-3 kernel rebuild and of the 288 x 256 conv kernel:
 #   base (VSR_F32_V8=0) | V8 | QKV 128x128 | QK^T 128x128 | P.V 128x128
 OUT=gpurun_out/r04_knobs; mkdir -p $OUT
-B="python bench.py --no-cpu-baseline --no-split-half --e2e-chunks 0 --steps 8 --warmup 2"
+B="python bench.py --full --no-cpu-baseline --no-split-half --e2e-chunks 0 --steps 8 --warmup 2"
 run() {   # name, env...
   name=$1; shift
   env "$@" timeout 600 $B > $OUT/$name.log 2>&1

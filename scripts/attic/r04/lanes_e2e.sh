@@ -14,4 +14,4 @@ run det_l1_b2 VSR_DET_LANES=1 VSR_BATCH_LANES=2 -- --mode sttn-det
 run det_l2_b2 VSR_DET_LANES=2 VSR_BATCH_LANES=2 -- --mode sttn-det
 run det_l3_b2 VSR_DET_LANES=3 VSR_BATCH_LANES=2 -- --mode sttn-det
 run pp_l2_b2 VSR_DET_LANES=2 VSR_BATCH_LANES=2 -- --mode propainter
-python bench.py --no-cpu-baseline > $OUT/bench.log 2>&1; grep '"metric"' $OUT/bench.log | cut -c1-300
+python bench.py --full --no-cpu-baseline > $OUT/bench.log 2>&1; grep '"metric"' $OUT/bench.log | cut -c1-300

@@ -8,7 +8,7 @@ for o in 1 0; do
 done
 (timeout 600 python -m pytest tests/test_gpu_kernels.py -q -x -k "256x256" 2>&1 | tail -3) > $OUT/pytest_kernels.log; tail -1 $OUT/pytest_kernels.log
 for prec in f16 split-format; do
-B="python bench.py --precision $prec --no-cpu-baseline --no-split-half --e2e-chunks 0 --steps 8 --warmup 2"
+B="python bench.py --full --precision $prec --no-cpu-baseline --no-split-half --e2e-chunks 0 --steps 8 --warmup 2"
 for i in 1 2; do
   for v in 1 0; do
     VSR_V7_ORDER=$v timeout 600 $B > $OUT/bench_${prec}_order${v}_$i.log 2>&1

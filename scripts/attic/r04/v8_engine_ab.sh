@@ -4,7 +4,7 @@
 OUT=gpurun_out/r04_v8e; mkdir -p $OUT
 (timeout 600 python -m pytest tests/test_gpu_kernels.py -q -x -k "288x256 or 128x64" 2>&1 | tail -15) > $OUT/pytest_kernels.log; tail -3 $OUT/pytest_kernels.log
 (timeout 900 python -m pytest tests/test_gpu_sttn.py -q -x 2>&1 | tail -15) > $OUT/pytest_sttn.log; tail -3 $OUT/pytest_sttn.log
-B="python bench.py --no-cpu-baseline --no-split-half --e2e-chunks 0 --steps 8 --warmup 2"
+B="python bench.py --full --no-cpu-baseline --no-split-half --e2e-chunks 0 --steps 8 --warmup 2"
 for i in 1 2; do
   for v in 1 0; do
     VSR_F32_V8=$v timeout 600 $B > $OUT/bench_v8_${v}_$i.log 2>&1

@@ -2,7 +2,7 @@
 # per-launch durations of the conv kernels inside the engine, single lane: the 288 x 256 kernel (default) and the 128 x 64 kernel
 # (VSR_F32_V8=0), grouped by grid size (= window size T); rocprofv3 kernel trace of two bench steps each
 OUT=gpurun_out/r04_v8t; mkdir -p $OUT; export TMPDIR=/tmp
-B="python bench.py --lanes 1 --steps 2 --warmup 1 --no-cpu-baseline --no-split-half --e2e-chunks 0"
+B="python bench.py --full --lanes 1 --steps 2 --warmup 1 --no-cpu-baseline --no-split-half --e2e-chunks 0"
 for v in 1 0; do
   VSR_F32_V8=$v rocprofv3 --kernel-trace --output-format csv -d $OUT/t$v -o r -- $B > $OUT/trace_$v.log 2>&1
   python - <<PY

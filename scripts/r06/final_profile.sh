@@ -3,7 +3,7 @@
 # on, and the default two-lane command) and of the f16 mode; per-ENGINE kernel stats of one propainter batch (scripts/stage_stats.py);
 # detector / RAFT / flow completion / LaMa stats; HBM traffic of every config (scripts/pmc_configs.py); e2e file-to-file; 2-rank dry run
 OUT=gpurun_out/r06_final; mkdir -p $OUT; export TMPDIR=/tmp
-python bench.py > $OUT/bench.log 2>&1; grep '"metric"' $OUT/bench.log | cut -c1-300
+python bench.py --full > $OUT/bench.log 2>&1; grep '"metric"' $OUT/bench.log | cut -c1-300
 python - <<'PY'
 import json
 d = [json.loads(l) for l in open("gpurun_out/r06_final/bench.log") if l.startswith("{")][-1]
@@ -13,7 +13,7 @@ for k, v in d.get("configs", {}).items():
     r = v.get("roofline") or {}
     print("  config", k, v.get("value"), v.get("unit"), "|", v.get("model_tflops"), "TF |", r.get("kernel"), r.get("achieved"), r.get("frac"), "traffic", r.get("traffic"), "hbm_gbps", v.get("hbm_gbps"), v.get("error"), v.get("leg_seconds"), "s")
 PY
-B="python bench.py --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work"
+B="python bench.py --full --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o r -- $B --lanes 1 > $OUT/trace.log 2>&1
 grep '"metric"' $OUT/trace.log > $OUT/bench_under_rocprof.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_lanes2 -o r -- $B > $OUT/trace_lanes2.log 2>&1
@@ -37,7 +37,7 @@ for p in f32 f16; do (timeout 900 python scripts/bench_e2e.py --clip $CLIP --fra
 rm -f $CLIP
 (timeout 900 python scripts/bench_e2e.py --frames 1200 --always-on --mode sttn-det 2>&1 | grep '"metric"') > $OUT/e2e_det.json; cut -c1-400 $OUT/e2e_det.json
 for a in "--res 720p --frames 300" "--res 1080p --frames 600"; do (timeout 300 python scripts/bench_cli.py $a 2>/dev/null | grep '^{') >> $OUT/cli.log; done; cut -c1-200 $OUT/cli.log
-VSR_BENCH_DRYRUN_1GPU=1 VSR_BENCH_MULTI_PP_FRAMES=20 VSR_PP_LANES=1 VSR_RAFT_LANES=1 VSR_BENCH_LEG_TIMEOUT=240 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 > $OUT/dryrun_2ranks.log 2>&1
+VSR_BENCH_DRYRUN_1GPU=1 VSR_BENCH_MULTI_PP_FRAMES=20 VSR_PP_LANES=1 VSR_RAFT_LANES=1 VSR_BENCH_LEG_TIMEOUT=240 timeout 900 python bench.py --full --gpus 2 --steps 2 --warmup 1 > $OUT/dryrun_2ranks.log 2>&1
 echo "dryrun rc=$?"; grep '^{' $OUT/dryrun_2ranks.log | python -c "
 import sys, json
 for l in sys.stdin:

@@ -2,7 +2,7 @@
 # round 6, first call: (a) the two-rank dry run of bench.py with the new N-rank legs of configs 5 and 4 (one GPU, gloo),
 # (b) HBM traffic of every configuration from PMC passes (scripts/pmc_configs.py)
 OUT=gpurun_out/r06_first; mkdir -p $OUT; export TMPDIR=/tmp
-VSR_BENCH_DRYRUN_1GPU=1 VSR_BENCH_MULTI_PP_FRAMES=20 VSR_PP_LANES=1 VSR_RAFT_LANES=1 VSR_BENCH_LEG_TIMEOUT=240 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 > $OUT/dryrun_2ranks.log 2>&1
+VSR_BENCH_DRYRUN_1GPU=1 VSR_BENCH_MULTI_PP_FRAMES=20 VSR_PP_LANES=1 VSR_RAFT_LANES=1 VSR_BENCH_LEG_TIMEOUT=240 timeout 900 python bench.py --full --gpus 2 --steps 2 --warmup 1 > $OUT/dryrun_2ranks.log 2>&1
 echo "dryrun rc=$?"; grep '^{' $OUT/dryrun_2ranks.log | python -c "
 import sys, json
 for l in sys.stdin:

@@ -8,7 +8,7 @@ run VSR_F16_V7_COMPANIONS=0
 run VSR_F16_V7_COMPANIONS=1
 run VSR_F16_V7_COMPANIONS=0
 run VSR_F16_V7_COMPANIONS=1
-B="python bench.py --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work --precision f16"
+B="python bench.py --full --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work --precision f16"
 for c in 0 1; do echo "=== 1080p f16 bench, companions $c" | tee -a $L; VSR_F16_V7_COMPANIONS=$c $B 2>/dev/null | grep '"metric"' | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().splitlines()[-1])

@@ -1,4 +1,4 @@
-B="python bench.py --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work"
+B="python bench.py --full --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work"
 run() { echo "=== $*"; env "$@" $B 2>/dev/null | grep '"metric"' | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().splitlines()[-1])

@@ -1,5 +1,5 @@
 OUT=gpurun_out/r06c; mkdir -p $OUT
-B="python bench.py --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work"
+B="python bench.py --full --no-cpu-baseline --no-configs --no-split-half --e2e-chunks 0 --no-full-work"
 L=$OUT/sttn_thin_ab.log; : > $L
 run() { echo "=== $*" | tee -a $L; env "$@" $B 2>/dev/null | grep '"metric"' | python -c "
 import sys, json

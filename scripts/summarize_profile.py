@@ -84,7 +84,7 @@ if dom and (dom, "FETCH_SIZE") in agg and (dom, "WRITE_SIZE") in agg:
             cal[c + "_KB_mean_copyBuffer"] = t / n
     out = {"kernel": dom, "launches": nf, "FETCH_SIZE_KB_mean": tf / nf, "WRITE_SIZE_KB_mean": tw / nw,
            "hbm_bytes_per_launch": int(round((2 * tf / nf + tw / nw) * 1024)), "calibration": cal,
-           "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `python bench.py --steps 1 --warmup 0 "
+           "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes over `python bench.py --full --steps 1 --warmup 0 "
                    "--no-cpu-baseline --no-split-half --e2e-chunks 0`; gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE counts 1/2 of "
                    "wide (16 B/lane) reads, WRITE_SIZE is exact KB (both checked on __amd_rocclr_copyBuffer in the same run, see "
                    "calibration), so bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024; mean over all launches of the symbol"}

@@ -1,5 +1,5 @@
-"""bench.py's launcher logic without a GPU: `python bench.py --gpus N` started with no launcher re-executes itself under
-torch.distributed.run with one rank per GPU (the driver's 8-GPU command), and every rank then stops at the first thing it needs --
+"""bench.py's launcher logic without a GPU: `python bench.py --gpus N` started with no launcher starts torch.distributed.run as a
+child process with one rank per GPU (the 8-GPU command), and every rank then stops at the first thing it needs --
 a GPU -- with bench.py's own message, not with the old "launch with torch.distributed.run" exit."""
 import os
 import subprocess
