@@ -112,6 +112,73 @@ def test_generator_strip_size_smoke(gen_engine, gpu_device):
     assert torch.equal(a, b)
 
 
+def _alternation_window(seed, t, lt, H, W):
+    frames, masks, ff, fb = propainter_inputs(seed, t, lt, H, W)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    m8 = d(masks[:, 0].astype(np.uint8))
+    return d(frames * (1 - masks)), d(ff), d(fb), m8
+
+
+def _fresh_equal(pp_sd, calls, run):
+    """each call's result on one engine (in sequence) equals, bit for bit, what a fresh engine gives for the same call"""
+    eng = PpEngine(device=0, state_dict=pp_sd)
+    got = [run(eng, c).clone() for c in calls]
+    torch.cuda.synchronize()
+    eng.close()
+    for c, g in zip(calls, got):
+        fresh = PpEngine(device=0, state_dict=pp_sd)
+        want = run(fresh, c)
+        torch.cuda.synchronize()
+        assert torch.equal(g, want), f"call {c[:2]} differs from a fresh engine's"
+        fresh.close()
+
+
+def test_generator_frame_count_alternation(built_lib, gpu_device, pp_sd):
+    """The sliding windows of a batch alternate their frame counts at one (lt, H, W), and the generator's workspace is cleared by
+    extent under a layout key without t (flow_engine.hip ensure_clean, "gen:"): forward with t = 7 -> 6 -> 8 -> 6 on one engine
+    gives what a fresh engine gives for each window, bit for bit -- a shorter window must not see the longer one's frames"""
+    lt, H, W = 5, 128, 192
+    calls = [(20 + i, t, _alternation_window(20 + i, t, lt, H, W)) for i, t in enumerate((7, 6, 8, 6))]
+    _fresh_equal(pp_sd, calls, lambda e, c: e.forward(c[2][0], c[2][1], c[2][2], c[2][3], c[2][3], lt))
+
+
+@pytest.mark.skipif(not switches.on("VSR_PP_ENC_CACHE"),
+                    reason="the per-frame encoder cache is switched off (VSR_PP_ENC_CACHE=0; default on since round 5)")
+def test_encoder_frame_count_alternation(built_lib, gpu_device, pp_sd):
+    """vsr_pp_encode with n = 6 -> 3 -> 6 frames on one engine (layout key "enc:" without n): features and tokens equal a fresh
+    engine's bit for bit"""
+    H, W = 128, 192
+    calls = [(30 + i, n, _alternation_window(30 + i, n, 2, H, W)) for i, n in enumerate((6, 3, 6))]
+
+    def run(e, c):
+        sel, _, _, m8 = c[2]
+        f, k = e.encode(sel, m8, m8, 2)
+        return torch.cat([f.reshape(-1), k.reshape(-1)])
+
+    _fresh_equal(pp_sd, calls, run)
+
+
+@pytest.mark.skipif(not switches.on("VSR_PP_ENC_CACHE"),
+                    reason="the per-frame encoder cache is switched off (VSR_PP_ENC_CACHE=0; default on since round 5)")
+def test_cached_forward_frame_count_alternation(built_lib, gpu_device, pp_sd):
+    """vsr_pp_forward_cached with t = 7 -> 6 -> 8 -> 6 at one (lt, H, W) (layout key "genc:" without t), each window encoded on the
+    same engine first: equal to a fresh engine's encode + forward_cached bit for bit"""
+    lt, H, W = 5, 128, 192
+    calls = [(40 + i, t, _alternation_window(40 + i, t, lt, H, W)) for i, t in enumerate((7, 6, 8, 6))]
+
+    def run(e, c):
+        t = c[1]
+        sel, ff, fb, m8 = c[2]
+        refs, local = list(range(t - 1, lt - 1, -1)), list(range(lt))
+        f1, k1 = e.encode(sel[refs].contiguous(), m8[refs].contiguous(), m8[refs].contiguous(), len(refs))
+        f2, _ = e.encode(sel[local].contiguous(), m8[local].contiguous(), m8[local].contiguous(), 0)
+        idx = [len(refs) + k for k in range(lt)] + [refs.index(k) for k in range(lt, t)]
+        flags = e.window_flags(m8[:lt].cpu().numpy())
+        return e.forward_cached(torch.cat([f1, f2]), k1, idx, ff, fb, m8, m8, lt, H, W, flags)
+
+    _fresh_equal(pp_sd, calls, run)
+
+
 @pytest.mark.skipif(not switches.on("VSR_PP_DECODE_BOX"),
                     reason="the generator's decoder box is switched off (VSR_PP_DECODE_BOX=0; default on since round 5)")
 @pytest.mark.parametrize("box", [(224, 360, 0, 0), (224, 360, 280, 1640), (0, 64, 0, 512), (120, 200, 1400, 1920)])
