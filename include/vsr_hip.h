@@ -464,6 +464,28 @@ int vsr_lama_read_buffer(vsr_lama_t* h, int buf, int64_t offset, int64_t count, 
 double vsr_lama_flops(vsr_lama_t* h, int B, int H, int W);
 
 /* ---------------------------------------------------------------------------------------
+ * --inpaint-mode opencv: `cv2.inpaint(frame, mask, 3, cv2.INPAINT_TELEA)` of backend/inpaint/opencv_inpaint.py:9, restated
+ * (OpenCV's fast-marching Telea fill; the statement is tests/_telea_statement.py, the design DESIGN.md).  One handle holds one
+ * mask's schedule ("plan"): fill order, T, levels and tap weights depend on the mask alone and are built on the host by
+ * set_mask; inpaint replays them on every frame, one workgroup per frame.
+ * ------------------------------------------------------------------------------------- */
+typedef struct vsr_telea vsr_telea_t;
+int vsr_telea_create(vsr_telea_t** out, int device, int radius);   /* device < 0: host-side plan only (plan tests); radius 1..5 */
+void vsr_telea_destroy(vsr_telea_t* h);
+/* mask: HOST uint8 [H][W], non-zero = fill; H, W >= 3.  Builds the plan and, with a device, uploads it (synchronous). */
+int vsr_telea_set_mask(vsr_telea_t* h, const uint8_t* mask_host, int H, int W);
+int64_t vsr_telea_plan_pixels(const vsr_telea_t* h);    /* P: masked pixels reached (0 for an empty mask or one with no band) */
+int vsr_telea_plan_levels(const vsr_telea_t* h);        /* L: groups of mutually independent pixels, run in order */
+int vsr_telea_plan_taps(const vsr_telea_t* h);          /* NT: taps per pixel (28 for radius 3) */
+/* read-back hooks of the replay tests; any pointer may be null.  Pixels come sorted by (level, step):
+ * yx int32 [P][2], step int32 [P] (index in the serial fill order), T float [P], level int32 [P] (1-based). */
+int vsr_telea_plan_read(const vsr_telea_t* h, int32_t* yx, int32_t* step, float* T, int32_t* level);
+int vsr_telea_plan_tmap(const vsr_telea_t* h, float* out);         /* T of the padded frame, float [(H+2)][(W+2)] */
+int vsr_telea_plan_weights(const vsr_telea_t* h, float* w, uint8_t* flags);   /* [NT][P] each, pixels in the order above */
+/* n frames uint8 [H][W][3] on the device, frame f at frames_dev + f * frame_stride bytes, masked pixels filled in place. */
+int vsr_telea_inpaint(vsr_telea_t* h, uint8_t* frames_dev, int64_t frame_stride, int n, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Text detector: the operators of the PP-OCRv5 detection inference programs the reference
  * loads through paddleocr (backend/tools/subtitle_detect.py:41-58, backend/models/V5/{ch_det,ch_det_fast}/inference.json).
  * NCHW fp32 device tensors; the host runner (backend/tools/ocr_det.py) walks the program and calls one launcher per op.

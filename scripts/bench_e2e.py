@@ -117,7 +117,7 @@ class InjectedDetection(ocr_det.TextDetection):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", required=True, choices=["sttn-det", "propainter", "lama"])
+    ap.add_argument("--mode", required=True, choices=["sttn-det", "propainter", "lama", "opencv"])
     ap.add_argument("--res", default="1080p", choices=sorted(RES))
     ap.add_argument("--frames", type=int, default=1200)
     ap.add_argument("--precision", default=None, help="propainter: f32 (default) or split")
@@ -157,6 +157,8 @@ def main():
         if args.precision:
             os.environ["VSR_PP_PRECISION"] = args.precision
         config.inpaintMode.value = InpaintMode.PROPAINTER
+    elif args.mode == "opencv":
+        config.inpaintMode.value = InpaintMode.OPENCV                        # no weights: the Telea fill needs only the mask
     else:
         ck = os.path.join(tmp, "big-lama.npz")
         np.savez(ck, **synth.make_lama_state_dict(0))

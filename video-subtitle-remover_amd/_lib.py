@@ -203,6 +203,16 @@ SIGNATURES = {
     "vsr_lama_read_buffer": (_I, [_P, _I, _L, _L, _P]),
     "vsr_lama_flops": (_D, [_P, _I, _I, _I]),
     "vsr_lama_plan_create": (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
+    "vsr_telea_create": (_I, [C.POINTER(_P), _I, _I]),
+    "vsr_telea_destroy": (None, [_P]),
+    "vsr_telea_set_mask": (_I, [_P, _P, _I, _I]),
+    "vsr_telea_plan_pixels": (_L, [_P]),
+    "vsr_telea_plan_levels": (_I, [_P]),
+    "vsr_telea_plan_taps": (_I, [_P]),
+    "vsr_telea_plan_read": (_I, [_P, _P, _P, _P, _P]),
+    "vsr_telea_plan_tmap": (_I, [_P, _P]),
+    "vsr_telea_plan_weights": (_I, [_P, _P, _P]),
+    "vsr_telea_inpaint": (_I, [_P, _P, _L, _I, _P]),
     "vsr_plan_consts": (_L, [_P, _P, _L]),
     "vsr_plan_destroy": (None, [_P]),
     "vsr_plan_num_buffers": (_I, [_P]),

@@ -1,11 +1,28 @@
-"""--inpaint-mode opencv (reference backend/inpaint/opencv_inpaint.py:1-16): cv2.inpaint on the CPU, one frame at a time.
+"""--inpaint-mode opencv with the reference's signature, running on the MI355X engine.
 
-Not on the accelerated path (out of scope as a kernel): the mode is a pass-through to OpenCV's own
-Telea inpainting, exactly the call the reference makes, and exists only where opencv-python does.  Without cv2 the command line
-refuses the mode (tools/args_handler.py) instead of failing after the detector pass."""
+Mirrors backend/inpaint/opencv_inpaint.py:
+  OpenCVInpaint()
+      inpaint(frame, mask) -> uint8 HxWx3            :8-10   cv2.inpaint(frame, mask, 3, cv2.INTER_LINEAR): the flag's value is
+                                                             1 = INPAINT_TELEA, radius 3
+      __call__(input_frames, input_mask) -> frames   :12-16  (the generic plugin contract of main.py:326)
+OpenCV's Telea fill is restated (tests/_telea_statement.py): the fast-marching order depends on the mask alone, so
+the engine builds it once per mask on the host and replays it on every frame in a HIP kernel.  Parity with cv2 itself is
+pinned only where cv2 can be imported (tests/test_gpu_telea.py).  The reference's own pass-through survives as an explicit
+choice, VSR_OPENCV_BACKEND=cv2, honoured only where cv2 imports; the default is the GPU path everywhere and has no CPU path.
+"""
+import os
+
+import numpy as np
+import torch
+
+from ...engine import TeleaEngine
+from .sttn_auto_inpaint import _device_index
+
+RADIUS = 3                                                                   # opencv_inpaint.py:9
 
 
 def available():
+    """whether opencv-python can be imported (only VSR_OPENCV_BACKEND=cv2 needs it)"""
     try:
         import cv2  # noqa: F401
         return True
@@ -13,14 +30,54 @@ def available():
         return False
 
 
-class OpenCVInpaint:
-    def __init__(self):
-        import cv2
+def _mask2d(mask):
+    m = np.asarray(mask)
+    if m.ndim == 3:                                                          # [H,W,1], as the other plugins' callers may pass
+        m = m[:, :, 0]
+    return np.ascontiguousarray(m, dtype=np.uint8)
 
-        self._cv2 = cv2
+
+class OpenCVInpaint:
+    accepts_device_frames = True      # __call__ also takes a uint8 [n,H,W,3] device tensor and inpaints it in place (tools/resident.py)
+
+    def __init__(self, device="cuda:0", engine=None):
+        self.device = device
+        self._cv2 = None
+        if engine is None and os.environ.get("VSR_OPENCV_BACKEND", "").lower() == "cv2" and available():
+            import cv2
+
+            self._cv2 = cv2
+            self.accepts_device_frames = False
+            self.engine = None
+        else:
+            self.engine = engine if engine is not None else TeleaEngine(device=_device_index(device), radius=RADIUS)
+
+    def clone(self):
+        """a second instance on the same device: its own engine and plan cache (tools/batch_lanes.py)"""
+        return OpenCVInpaint(self.device)
+
+    def close(self):
+        if self.engine is not None:
+            self.engine.close()
 
     def inpaint(self, frame, mask):
-        return self._cv2.inpaint(frame, mask, 3, self._cv2.INTER_LINEAR)      # opencv_inpaint.py:9 (flag value 1 = INPAINT_TELEA)
+        return self([frame], mask)[0]
 
-    def __call__(self, frames, mask):
-        return [self.inpaint(frame, mask) for frame in frames]
+    def __call__(self, input_frames, input_mask):
+        """input_frames: the reference's list of HxWx3 uint8 BGR arrays (fresh arrays come back, inputs untouched), or -- the
+        HBM-resident loop of main.SubtitleRemover, tools/resident.py -- a uint8 [n,H,W,3] device tensor, which is inpainted IN
+        PLACE and returned."""
+        mask = _mask2d(input_mask)
+        if self._cv2 is not None:
+            return [self._cv2.inpaint(f, mask, RADIUS, self._cv2.INPAINT_TELEA) for f in input_frames]
+        if isinstance(input_frames, torch.Tensor):
+            if input_frames.shape[0]:
+                self.engine.inpaint(input_frames, mask)
+            return input_frames
+        if len(input_frames) == 0:
+            return []
+        if not mask.any():
+            return [np.array(f, copy=True) for f in input_frames]
+        frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(self.engine.device)
+        out = self.engine.inpaint(frames, mask).cpu().numpy()
+        return [out[i] for i in range(out.shape[0])]

@@ -3,11 +3,11 @@
     python -m vsr_amd.backend.main -i IN -o OUT [-c YMIN YMAX XMIN XMAX]... [--inpaint-mode sttn-auto]
 
 Same flags, enum names and call order as the reference (backend/main.py:473-488, tools/args_handler.py:6-30):
-SubtitleRemover(path).sub_areas / .ab_sections / .video_out_path / .run() with the modes sttn-auto, sttn-det, lama and
-propainter on the MI355X engines.  Frames are read and written through tools/video_io.py (raw containers, an ffmpeg pipe
+SubtitleRemover(path).sub_areas / .ab_sections / .video_out_path / .run() with the modes sttn-auto, sttn-det, lama,
+propainter and opencv on the MI355X engines.  Frames are read and written through tools/video_io.py (raw containers, an ffmpeg pipe
 when a binary exists; `-o OUT` is written or the run fails -- there is no silent in-memory sink for a file input); audio is
-muxed with the reference's two ffmpeg commands when ffmpeg exists (main.py:418-460).  GUI transport, temp files and the
-opencv mode stay with the reference (surface only, not accelerated).
+muxed with the reference's two ffmpeg commands when ffmpeg exists (main.py:418-460).  GUI transport and temp files stay
+with the reference (surface only, not accelerated).
 """
 import os
 import sys
@@ -496,12 +496,11 @@ class SubtitleRemover:
             self.propainter_mode(None, propainter_inpaint=getattr(self, "propainter_inpaint", None),
                                  text_detector=self._default_detector(), scene_div_points=getattr(self, "scene_div_points", None))
         elif mode == InpaintMode.OPENCV:
-            # main.py:383-384: cv2.inpaint (Telea, radius 3) on the CPU, frame by frame -- not part of the MI355X path (SURVEY 2.1:
-            # surface only).  With opencv-python installed it is the reference's own two lines; without it args_handler has
-            # already refused the mode.
+            # main.py:383-384: cv2.inpaint (Telea, radius 3), restated as a level replay on the GPU (inpaint/opencv_inpaint.py)
             from .inpaint.opencv_inpaint import OpenCVInpaint
 
-            self.video_inpaint(None, OpenCVInpaint(), text_detector=self._default_detector())
+            plugin = getattr(self, "opencv_inpaint", None) or OpenCVInpaint(self.device)
+            self.video_inpaint(None, plugin, text_detector=self._default_detector())
         else:
             raise Exception(f"inpaint mode: {mode} not implemented")     # main.py:386
         if self._video_writer is not None:

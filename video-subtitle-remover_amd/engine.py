@@ -819,3 +819,88 @@ class LamaEngine:
             check(lib.vsr_lama_inpaint(self._h, C.c_void_p(images.data_ptr()), istr, C.c_void_p(m.data_ptr()), mstride, B, H, W,
                                        C.c_void_p(out.data_ptr()), ostr, _stream_ptr()))
         return out
+
+
+class TeleaEngine:
+    """--inpaint-mode opencv: OpenCV's Telea fill (cv2.inpaint(frame, mask, 3, INPAINT_TELEA), reference
+    backend/inpaint/opencv_inpaint.py:9) as a level replay on the GPU.  The serial fast-marching sweep depends on the mask alone:
+    it runs once per mask on the host (csrc/telea_plan.cpp) and every frame replays its schedule, one workgroup per frame.  The
+    plans of the last `max_plans` masks are kept, keyed by the mask's bytes: an interval's batches and the lanes of
+    tools/batch_lanes.py present the same mask again and again."""
+
+    def __init__(self, device=0, radius=3, max_plans=4):
+        if device is not None and device >= 0:
+            require_gpu()
+        self.device_index = -1 if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index) if self.device_index >= 0 else torch.device("cpu")
+        self.radius = int(radius)
+        self.max_plans = int(max_plans)
+        self._plans = {}                 # (H, W, mask bytes) -> handle; insertion order = least recently used first
+        self.plan_builds = 0
+        self.plan_hits = 0
+        h = C.c_void_p()                 # arguments are checked now, not at the first mask
+        check(lib.vsr_telea_create(C.byref(h), self.device_index, self.radius))
+        lib.vsr_telea_destroy(h)
+
+    def close(self):
+        for h in getattr(self, "_plans", {}).values():
+            lib.vsr_telea_destroy(h)
+        self._plans = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def plan(self, mask):
+        """the handle holding `mask`'s schedule (host uint8 [H,W], non-zero = fill): cached, or built and uploaded now"""
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert mask.ndim == 2, "mask must be [H, W]"
+        key = (mask.shape[0], mask.shape[1], mask.tobytes())
+        h = self._plans.pop(key, None)
+        if h is None:
+            h = C.c_void_p()
+            check(lib.vsr_telea_create(C.byref(h), self.device_index, self.radius))
+            try:
+                if self.device_index >= 0:
+                    with torch.cuda.device(self.device):
+                        check(lib.vsr_telea_set_mask(h, mask.ctypes.data_as(C.c_void_p), mask.shape[0], mask.shape[1]))
+                else:
+                    check(lib.vsr_telea_set_mask(h, mask.ctypes.data_as(C.c_void_p), mask.shape[0], mask.shape[1]))
+            except Exception:
+                lib.vsr_telea_destroy(h)
+                raise
+            self.plan_builds += 1
+            while len(self._plans) >= self.max_plans:
+                lib.vsr_telea_destroy(self._plans.pop(next(iter(self._plans))))   # synchronises the device before freeing
+        else:
+            self.plan_hits += 1
+        self._plans[key] = h
+        return h
+
+    def plan_stats(self, mask):
+        h = self.plan(mask)
+        return {"pixels": int(lib.vsr_telea_plan_pixels(h)), "levels": int(lib.vsr_telea_plan_levels(h)),
+                "taps": int(lib.vsr_telea_plan_taps(h))}
+
+    def inpaint(self, frames, mask, out=None):
+        """frames uint8 [n,H,W,3] on the GPU (each frame contiguous), mask HOST uint8 [H,W] (numpy; non-zero = fill).  out=None
+        or out=frames: in place; another tensor: the frames are copied there first and filled there.  Returns the filled tensor."""
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 4 and frames.shape[3] == 3
+        n, H, W, _ = frames.shape
+        if isinstance(mask, torch.Tensor):
+            mask = mask.cpu().numpy()
+        assert tuple(mask.shape) == (H, W), f"mask {tuple(mask.shape)} does not fit frames {(H, W)}"
+        if out is not None and out.data_ptr() != frames.data_ptr():
+            assert out.shape == frames.shape and out.dtype == torch.uint8 and out.device == frames.device
+            out.copy_(frames)
+            frames = out
+        if n == 0:
+            return frames
+        assert frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) == 3 * W, "frames must be contiguous [H,W,3]"
+        stride = frames.stride(0) if n > 1 else H * W * 3
+        h = self.plan(mask)
+        with torch.cuda.device(frames.device):
+            check(lib.vsr_telea_inpaint(h, C.c_void_p(frames.data_ptr()), stride, n, _stream_ptr()))
+        return frames
