@@ -585,6 +585,23 @@ int vsr_io_yuv_to_bgr(const uint8_t* planes_dev, int64_t frame_bytes, int H, int
 /* bgr_dev uint8 [nframes][H][W][3] -> records [Y][U][V]; subsample_420: chroma = rounded mean of each 2x2 block (edges repeated) */
 int vsr_io_bgr_to_yuv(const uint8_t* bgr_dev, int H, int W, int subsample_420, int full_range, uint8_t* planes_dev,
                       int64_t frame_bytes, int nframes, void* stream);
+/* The source's own format: depth 8 / 10 / 12 (above 8 bits: 16-bit little-endian samples, planes_dev and frame_bytes even), chroma_w in
+ * {0 (mono), W, (W+1)/2}, chroma_h in {H, (H+1)/2}, either range.  The constants of a depth come from the 8-bit ones on the host
+ * (studio range: unchanged, the shifts grow by depth - 8; full range: rescaled by 255 * 2^(depth-8) / (2^depth - 1), floor(x + 0.5) in
+ * double); vsr_io_color_constants hands them out: [ky, krv, kgu, kgv, kbu, encode rows Y / U / V over (R, G, B), luma offset, chroma
+ * offset, peak, depth - 8].  Bad arguments return VSR_ERR_ARG and launch nothing. */
+int vsr_io_color_constants(int depth, int full_range, int32_t* out18);
+/* stored samples above 2^depth - 1 are clipped before decoding; chroma by nearest replication */
+int vsr_io_planes_to_bgr(const void* planes_dev, int64_t frame_bytes, int H, int W, int chroma_w, int chroma_h, int depth, int full_range,
+                         uint8_t* bgr_dev, int nframes, void* stream);
+/* sub-sampled chroma = rounded mean of the block (2x1: (a + b + 1) >> 1, 2x2: (sum + 2) >> 2), edge pixels repeated.  With
+ * src_planes_dev (records of the same format, src_frame_bytes apart) the keep rule applies: a luma sample whose pixel decodes from the
+ * source to exactly the frame's colour, and a chroma sample whose whole block does, is copied from the source, everything else is
+ * encoded (backend/tools/video_io.py keep_record is the definition).  In place (planes_dev == src_planes_dev with frame_bytes ==
+ * src_frame_bytes) WORKS; any other overlap of the two ranges returns VSR_ERR_ARG. */
+int vsr_io_bgr_to_planes(const uint8_t* bgr_dev, int H, int W, int chroma_w, int chroma_h, int depth, int full_range,
+                         const void* src_planes_dev /* NULL: plain encode */, int64_t src_frame_bytes, void* planes_dev,
+                         int64_t frame_bytes, int nframes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),

@@ -165,6 +165,9 @@ SIGNATURES = {
     "vsr_gemm_plan_destroy": (None, [_P]),
     "vsr_io_yuv_to_bgr": (_I, [_P, _L, _I, _I, _I, _I, _I, _P, _I, _P]),
     "vsr_io_bgr_to_yuv": (_I, [_P, _I, _I, _I, _I, _P, _L, _I, _P]),
+    "vsr_io_color_constants": (_I, [_I, _I, _P]),
+    "vsr_io_planes_to_bgr": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "vsr_io_bgr_to_planes": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _L, _P, _L, _I, _P]),
     "vsr_launch_bgr2hsv_u8": (_I, [_P, _P, _L, _P]),
     "vsr_launch_absdiff_sums_u8x3": (_I, [_P, _I, _L, _P, _P]),
     "vsr_pp_create": (_I, [_I, C.POINTER(_P)]),

@@ -20,7 +20,7 @@ import torch
 
 from ..config import config
 from ..tools.inpaint_tools import get_inpaint_area_by_mask, is_frame_number_in_ab_sections, threshold_mask
-from ..tools.video_io import ArrayWriter, open_video
+from ..tools.video_io import ArrayWriter, device_bgr_to_planes, device_planes_to_bgr, open_video
 from ...engine import SttnEngine
 
 
@@ -94,8 +94,8 @@ class STTNInpaint:
 class _ResidentFrames:
     """the decoded frames of a chunk that stay in HBM while its strip rows are away (len() = frames actually read)"""
 
-    def __init__(self, full, n):
-        self.full, self.n = full, n
+    def __init__(self, full, n, planes=None):
+        self.full, self.n, self.planes = full, n, planes     # planes: the chunk's stored records, for a sink that keeps untouched samples
 
     def __len__(self):
         return self.n
@@ -262,9 +262,6 @@ class STTNAutoInpaint:
     def _run_rank_local(self, local, dist, rank, engine, ranges, mask, inpaint_area, size, ab_sections, tick, total):
         """the chunk loop of _run with per-rank file access: chunk i's stored planes -> pinned -> HBM -> BGR (vsr_io_yuv_to_bgr) ->
         vsr_sttn_auto_chunk in place on the whole frames -> planes (vsr_io_bgr_to_yuv) -> pinned -> the sink, at the records' offsets"""
-        import ctypes as C
-
-        from ..._lib import check, lib
         from ..tools import rank_io
         from ..tools.pinned import PinnedPool
 
@@ -290,8 +287,7 @@ class STTNAutoInpaint:
             tensors[t.numpy().ctypes.data] = t
             return t.numpy()
 
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        cur = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        cur = lambda: torch.cuda.current_stream(dev).cuda_stream
 
         def work(i, inp, out):
             s, _ = ranges[i]
@@ -299,11 +295,11 @@ class STTNAutoInpaint:
             ti, to = tensors[inp.ctypes.data][:k], tensors[out.ctypes.data][:k]
             with torch.cuda.device(dev):
                 d_in[:k].copy_(ti, non_blocking=True)
-                check(lib.vsr_io_yuv_to_bgr(ptr(d_in), rf["frame_bytes"], H, W, rf["cw"], rf["ch"], int(rf["full_range"]), ptr(full), k, cur()))
+                device_planes_to_bgr(rf, d_in.data_ptr(), H, W, full.data_ptr(), k, cur())
                 sel = [j - s for j in range(s, s + k) if is_frame_number_in_ab_sections(j, ab_sections)]
                 if sel:
                     engine.auto_chunk(full[:k], dmask, inpaint_area, sel=None if len(sel) == k else sel, mask_host=mask_host)
-                check(lib.vsr_io_bgr_to_yuv(ptr(full), H, W, int(wf["subsample_420"]), int(wf["full_range"]), ptr(d_out), wf["frame_bytes"], k, cur()))
+                device_bgr_to_planes(wf, full.data_ptr(), H, W, d_out.data_ptr(), k, cur(), d_in.data_ptr(), rf, path="the by-offset chunk loop")
                 to.copy_(d_out[:k], non_blocking=True)
                 torch.cuda.current_stream(dev).synchronize()
 
@@ -342,10 +338,6 @@ class STTNAutoInpaint:
         rows are copied out for the owner of the chunk; on the way back the rows are patched in, vsr_io_bgr_to_yuv converts and the
         planes come down into pinned memory for the writer thread.  The host touches no pixel: the reference's loop
         (sttn_auto_inpaint.py:254-262 read, :314-328 write) is cv2 / libswscale work on the CPU, 47 + 26 ms per 1080p frame in numpy."""
-        import ctypes as C
-
-        from ..._lib import check, lib
-
         (rf, wf), (H, W), (y_lo, y_hi) = fmt, size, rows
         dev = engine.device
         maxn = max((e - s for s, e in ranges), default=0)
@@ -370,8 +362,9 @@ class STTNAutoInpaint:
         d_in = torch.empty((maxn, rf["frame_bytes"]), dtype=u8, device=dev)
         d_out = torch.empty((maxn, wf["frame_bytes"]), dtype=u8, device=dev)
         free, turn = [], {"in": 0, "out": 0}
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        cur = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        keep = bool(wf.get("keep"))                      # the sink keeps untouched samples: a chunk's stored planes stay until its store
+        free_planes = []
+        cur = lambda: torch.cuda.current_stream(dev).cuda_stream
 
         def load(i, out):                                # rank 0, called on the io stream of the chunk loop
             s, e = ranges[i]
@@ -384,17 +377,18 @@ class STTNAutoInpaint:
             if k < e - s:
                 print(f"Warning: Failed to read frame {s + k}.")                 # :259-261: the chunk ends with the frames read so far
             full = free.pop() if free else torch.empty((maxn, H, W, 3), dtype=u8, device=dev)
+            planes = d_in if not keep else (free_planes.pop() if free_planes else torch.empty((maxn, rf["frame_bytes"]), dtype=u8, device=dev))
             if k:
-                d_in[:k].copy_(hb[:k], non_blocking=pinned)    # (a pageable source is copied before the call returns)
+                planes[:k].copy_(hb[:k], non_blocking=pinned)  # (a pageable source is copied before the call returns)
                 if pinned:
                     ev_in[b] = torch.cuda.Event()
                     ev_in[b].record(torch.cuda.current_stream(dev))
-                check(lib.vsr_io_yuv_to_bgr(ptr(d_in), rf["frame_bytes"], H, W, rf["cw"], rf["ch"], int(rf["full_range"]), ptr(full), k, cur()))
+                device_planes_to_bgr(rf, planes.data_ptr(), H, W, full.data_ptr(), k, cur())
                 out[:k].copy_(full[:k, y_lo:y_hi])
             else:
                 print(f"Warning: No valid frames found in range {s + 1}-{e}. Skipping this segment.")
             out[k:].zero_()
-            kept[i] = _ResidentFrames(full, k)
+            kept[i] = _ResidentFrames(full, k, planes if keep else None)
 
         def store(i, rows_dev):                          # rank 0, io stream, chunk order
             kf = kept.pop(i)
@@ -402,7 +396,8 @@ class STTNAutoInpaint:
             if k:
                 kf.full[:k, y_lo:y_hi].copy_(rows_dev[:k])
                 b = turn["out"] = turn["out"] ^ 1
-                check(lib.vsr_io_bgr_to_yuv(ptr(kf.full), H, W, int(wf["subsample_420"]), int(wf["full_range"]), ptr(d_out), wf["frame_bytes"], k, cur()))
+                device_bgr_to_planes(wf, kf.full.data_ptr(), H, W, d_out.data_ptr(), k, cur(),
+                                     kf.planes.data_ptr() if kf.planes is not None else None, rf, path="the resident chunk loop")
                 hb, pinned = host_buf("out", b)
                 hb[:k].copy_(d_out[:k], non_blocking=pinned)
                 ev = torch.cuda.Event()
@@ -412,6 +407,8 @@ class STTNAutoInpaint:
                 for _ in range(k):
                     tick(None, None)
             free.append(kf.full)
+            if kf.planes is not None:
+                free_planes.append(kf.planes)
 
         store.close = pool.close                         # called by _run when the loop is over
         return load, store

@@ -22,7 +22,7 @@ from .tools.args_handler import parse_args
 from .tools.constant import InpaintMode
 from .tools.inpaint_tools import batch_generator, create_mask, expand_frame_ranges
 from .tools.subtitle_detect import SubtitleDetect
-from .tools.video_io import IMAGE_EXTS, ArrayWriter, AsyncWriter, ffmpeg_path, open_video, open_writer
+from .tools.video_io import IMAGE_EXTS, ArrayWriter, AsyncWriter, ffmpeg_path, open_video, open_writer, y4m_out_mode
 
 
 class SubtitleRemover:
@@ -66,9 +66,20 @@ class SubtitleRemover:
     @property
     def video_writer(self):
         if self._video_writer is None:
-            sink = open_writer(self.video_out_path, self.fps, (self.frame_width, self.frame_height), frames=self.frame_count)
+            sink = open_writer(self.video_out_path, self.fps, (self.frame_width, self.frame_height), frames=self.frame_count,
+                               like=self._y4m_like())
             self._video_writer = AsyncWriter(sink)
         return self._video_writer
+
+    def _y4m_like(self):
+        """VSR_Y4M_OUT=source (--y4m-out source): a *.y4m sink takes the format of the *.y4m source and keeps the samples the run did not
+        change (tools/video_io.py Y4mWriter like=...); the one place that turns the switch into a writer argument.  None: today's sink."""
+        out = self.video_out_path
+        if y4m_out_mode() != "source" or out is None or os.path.splitext(os.fspath(out))[1].lower() != ".y4m":
+            return None
+        if not self.is_path or os.path.splitext(os.fspath(self.video_path))[1].lower() != ".y4m":
+            raise RuntimeError(f"VSR_Y4M_OUT=source needs a *.y4m input to take the format from; the input is {self.video_path!r}")
+        return os.fspath(self.video_path)
 
     @video_writer.setter
     def video_writer(self, w):
@@ -143,10 +154,10 @@ class SubtitleRemover:
         try:
             fmts = ResidentClip.formats(reader, self.video_writer)
             info = reader.info()
-            if fmts is None or not ResidentClip.fits(info["len"], info["H_ori"], info["W_ori"]):
+            if fmts is None or not ResidentClip.fits(info["len"], info["H_ori"], info["W_ori"], fmts[0]["frame_bytes"] if fmts[1].get("keep") else 0):
                 return None
             t0 = time.time()
-            clip = ResidentClip.load(reader, fmts[0], info["len"], info["H_ori"], info["W_ori"], self.device)
+            clip = ResidentClip.load(reader, fmts[0], info["len"], info["H_ori"], info["W_ori"], self.device, keep_planes=bool(fmts[1].get("keep")))
             self.phase_seconds["read + upload + YUV->BGR"] = time.time() - t0
             return clip, fmts[1]
         finally:
@@ -475,6 +486,8 @@ class SubtitleRemover:
 
     def run(self):
         start_time = time.time()
+        if self._video_writer is None and self.is_path:
+            self._y4m_like()                                             # a sink that cannot be made fails before any work is done
         if len(self.sub_areas) == 0:
             self.sub_areas.append((0, self.frame_height, 0, self.frame_width))
         mode = config.inpaintMode.value
@@ -515,6 +528,8 @@ class SubtitleRemover:
 def main(argv=None):
     args = parse_args(argv)
     config.inpaintMode.value = args.inpaint_mode
+    if args.y4m_out is not None:
+        os.environ["VSR_Y4M_OUT"] = args.y4m_out
     sr = SubtitleRemover(args.input)
     sr.sub_areas = [tuple(c) for c in args.subtitle_area_coords]
     if args.output is not None:

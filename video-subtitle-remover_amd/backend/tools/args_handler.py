@@ -17,6 +17,9 @@ def build_parser():
     parser.add_argument("--inpaint-mode", type=str, default="sttn-auto",
                         choices=[mode.name.lower().replace("_", "-") for mode in InpaintMode],
                         help="Inpaint mode, default is sttn-auto")
+    # not in the reference: what a *.y4m sink holds (overrides VSR_Y4M_OUT)
+    parser.add_argument("--y4m-out", type=str, default=None, choices=["444", "source"],
+                        help="*.y4m output: 444 = 8-bit 4:4:4 (default), source = the format of the *.y4m input, untouched samples kept")
     return parser
 
 

@@ -11,20 +11,20 @@ sttn-auto only).
 Eligible: a raw planar source and sink whose colour conversion runs on the GPU (*.y4m, tools/video_io.py), one process, and a clip
 that fits VSR_RESIDENT_GB (default 64) as BGR.  Anything else keeps the host-frame loop; VSR_IO_RESIDENT=0 forces it.
 """
-import ctypes as C
 import os
 
 import torch
 
-from ..._lib import check, lib
+from .video_io import device_bgr_to_planes, device_planes_to_bgr
 
 
 class ResidentClip:
     BATCH = 32
 
-    def __init__(self, frames, fmt_in):
+    def __init__(self, frames, fmt_in, planes=None):
         self.frames = frames                     # uint8 [N,H,W,3] BGR on the device
         self.fmt_in = fmt_in
+        self.planes = planes                     # uint8 [N,frame_bytes]: the stored records, kept for a writer that keeps untouched samples
 
     @staticmethod
     def formats(reader, writer):
@@ -36,16 +36,19 @@ class ResidentClip:
         return (rf, wf) if rf is not None and wf is not None else None
 
     @staticmethod
-    def fits(n, H, W):
-        return n * H * W * 3 <= float(os.environ.get("VSR_RESIDENT_GB", "64")) * 2 ** 30
+    def fits(n, H, W, keep_bytes=0):
+        """keep_bytes: bytes of a stored record when the records stay in HBM next to the BGR frames (a keeping writer), else 0"""
+        return n * (H * W * 3 + keep_bytes) <= float(os.environ.get("VSR_RESIDENT_GB", "64")) * 2 ** 30
 
     @classmethod
-    def load(cls, reader, rf, n, H, W, device):
-        """read the stored planes of the whole clip, BATCH frames at a time through two pinned buffers, convert on the device"""
+    def load(cls, reader, rf, n, H, W, device, keep_planes=False):
+        """read the stored planes of the whole clip, BATCH frames at a time through two pinned buffers, convert on the device.
+        keep_planes: the records stay in HBM (uploaded straight into one tensor, converted from it) for store()'s keep rule."""
         dev = torch.device(device)
         frames = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
         pins = [torch.empty((cls.BATCH, rf["frame_bytes"]), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        dplanes = [torch.empty((cls.BATCH, rf["frame_bytes"]), dtype=torch.uint8, device=dev) for _ in range(2)]
+        planes = torch.empty((n, rf["frame_bytes"]), dtype=torch.uint8, device=dev) if keep_planes else None
+        dplanes = [torch.empty((cls.BATCH, rf["frame_bytes"]), dtype=torch.uint8, device=dev) for _ in range(2)] if planes is None else None
         events = [None, None]
         got, b = 0, 0
         with torch.cuda.device(dev):
@@ -56,9 +59,9 @@ class ResidentClip:
                 want = min(cls.BATCH, n - got)
                 k = reader.read_planes_into(pins[b].numpy()[:want])
                 if k:
-                    dplanes[b][:k].copy_(pins[b][:k], non_blocking=True)
-                    check(lib.vsr_io_yuv_to_bgr(C.c_void_p(dplanes[b].data_ptr()), rf["frame_bytes"], H, W, rf["cw"], rf["ch"], int(rf["full_range"]),
-                                                C.c_void_p(frames[got:].data_ptr()), k, C.c_void_p(stream.cuda_stream)))
+                    up = dplanes[b] if planes is None else planes[got:]
+                    up[:k].copy_(pins[b][:k], non_blocking=True)
+                    device_planes_to_bgr(rf, up.data_ptr(), H, W, frames[got:].data_ptr(), k, stream.cuda_stream)
                     events[b] = torch.cuda.Event()
                     events[b].record(stream)
                 got += k
@@ -67,7 +70,7 @@ class ResidentClip:
                     frames = frames[:got]
                     break
             torch.cuda.synchronize(dev)
-        return cls(frames, rf)
+        return cls(frames, rf, planes[:got] if planes is not None else None)
 
     def __len__(self):
         return int(self.frames.shape[0])
@@ -86,8 +89,8 @@ class ResidentClip:
             stream = torch.cuda.current_stream(dev)
             for s in range(lo, hi, self.BATCH):
                 k = min(self.BATCH, hi - s)
-                check(lib.vsr_io_bgr_to_yuv(C.c_void_p(self.frames[s:].data_ptr()), H, W, int(wf["subsample_420"]), int(wf["full_range"]),
-                                            C.c_void_p(dout[b].data_ptr()), wf["frame_bytes"], k, C.c_void_p(stream.cuda_stream)))
+                device_bgr_to_planes(wf, self.frames[s:].data_ptr(), H, W, dout[b].data_ptr(), k, stream.cuda_stream,
+                                     self.planes[s:].data_ptr() if self.planes is not None else None, self.fmt_in, path="the resident clip")
                 pins[b][:k].copy_(dout[b][:k], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(stream)

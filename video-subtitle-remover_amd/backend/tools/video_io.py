@@ -8,12 +8,14 @@ reading and writing overlap the GPU work, and a loud failure when nothing can se
   source                      sink
   ArrayVideo (in memory)      ArrayWriter / CountingWriter
   *.npy   uint8 [N,H,W,3] BGR NpyWriter         (memory-mapped, lossless: the parity container)
-  *.y4m   YUV4MPEG2           Y4mWriter         (C444 / C420 / mono, BT.601; what `ffmpeg -i x.mp4 x.y4m` writes; the colour
-                                                conversion runs on the GPU, csrc/io_kernels.hip)
+  *.y4m   YUV4MPEG2           Y4mWriter         (C444 / C422 / C420 / mono at 8, 10 or 12 bits, BT.601; what `ffmpeg -i x.mp4 x.y4m`
+                                                writes; the colour conversion runs on the GPU, csrc/io_kernels.hip; VSR_Y4M_OUT=source:
+                                                the sink takes the source's format and keeps the samples nothing changed)
   anything else               FFmpegVideoWriter (needs an `ffmpeg` on PATH or $VSR_FFMPEG; else cv2 if importable; else an error)
 """
 import os
 import queue
+import re
 import shutil
 import subprocess
 import threading
@@ -163,34 +165,177 @@ class NpyWriter:
 
 
 # BT.601 studio-swing integer matrices (the ones libswscale and OpenCV use for 8-bit YCbCr <-> RGB), 16.16 fixed point
-def _yuv_to_bgr(y, u, v, full_range):
-    y = y.astype(np.int32)
-    u = u.astype(np.int32) - 128
-    v = v.astype(np.int32) - 128
+_DEC8 = {False: (76309, 104597, -25675, -53279, 132201), True: (65536, 91881, -22554, -46802, 116130)}        # ky, krv, kgu, kgv, kbu
+_ENC8 = {False: (16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681),                               # rows Y, U, V over (R, G, B)
+         True: (19595, 38470, 7471, -11059, -21709, 32768, 32768, -27439, -5329)}
+DEPTHS = (8, 10, 12)
+
+
+def color_constants(depth, full_range):
+    """{"dec": 5 ints, "enc": 9 ints, "yoff", "coff", "peak", "s"} of one depth and range.  Studio range keeps the 8-bit constants (the
+    shifts grow by s = depth - 8); full range has its peak white at 2^depth - 1 and not at 255 << s, so the 8-bit constants are
+    rescaled once, floor(x + 0.5) in double -- the expression the launcher in csrc/io_kernels.hip uses (vsr_io_color_constants)."""
+    if depth not in DEPTHS:
+        raise ValueError(f"depth {depth} is not supported ({', '.join(map(str, DEPTHS))} are)")
+    full_range, s = bool(full_range), depth - 8
+    peak = (1 << depth) - 1
+    dec, enc = _DEC8[full_range], _ENC8[full_range]
     if full_range:
-        c = y << 16
-        r = (c + 91881 * v + 32768) >> 16
-        g = (c - 22554 * u - 46802 * v + 32768) >> 16
-        b = (c + 116130 * u + 32768) >> 16
-    else:
-        c = 76309 * (y - 16)
-        r = (c + 104597 * v + 32768) >> 16
-        g = (c - 25675 * u - 53279 * v + 32768) >> 16
-        b = (c + 132201 * u + 32768) >> 16
+        dec = tuple(int(np.floor(float(k) * float(255 << s) / float(peak) + 0.5)) for k in dec)
+        enc = tuple(int(np.floor(float(k) * float(peak) / float(255 << s) + 0.5)) for k in enc)
+    return {"dec": dec, "enc": enc, "yoff": 0 if full_range else 16 << s, "coff": 128 << s, "peak": peak, "s": s}
+
+
+def _yuv_to_bgr(y, u, v, full_range, depth=8):
+    k = color_constants(depth, full_range)
+    ky, krv, kgu, kgv, kbu = k["dec"]
+    rnd, sh = 1 << (15 + k["s"]), 16 + k["s"]
+    y = np.minimum(y.astype(np.int32), k["peak"])         # stored samples above the peak come from outside the program
+    u = np.minimum(u.astype(np.int32), k["peak"]) - k["coff"]
+    v = np.minimum(v.astype(np.int32), k["peak"]) - k["coff"]
+    c = ky * (y - k["yoff"])
+    r = (c + krv * v + rnd) >> sh
+    g = (c + kgu * u + kgv * v + rnd) >> sh
+    b = (c + kbu * u + rnd) >> sh
     return np.clip(np.stack([b, g, r], axis=-1), 0, 255).astype(np.uint8)
 
 
-def _bgr_to_yuv(frame, full_range):
-    b, g, r = (frame[..., k].astype(np.int32) for k in range(3))
-    if full_range:
-        y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16
-        u = ((-11059 * r - 21709 * g + 32768 * b + 32768) >> 16) + 128
-        v = ((32768 * r - 27439 * g - 5329 * b + 32768) >> 16) + 128
+def _bgr_to_yuv(frame, full_range, depth=8):
+    k = color_constants(depth, full_range)
+    e = k["enc"]
+    rnd, sh = 1 << (15 - k["s"]), 16 - k["s"]
+    b, g, r = (frame[..., i].astype(np.int32) for i in range(3))
+    y = ((e[0] * r + e[1] * g + e[2] * b + rnd) >> sh) + k["yoff"]
+    u = ((e[3] * r + e[4] * g + e[5] * b + rnd) >> sh) + k["coff"]
+    v = ((e[6] * r + e[7] * g + e[8] * b + rnd) >> sh) + k["coff"]
+    dt = np.uint8 if depth == 8 else np.dtype("<u2")
+    return (np.clip(p, 0, k["peak"]).astype(dt) for p in (y, u, v))
+
+
+# ---- records of one format: {"W", "H", "cw", "ch", "depth", "full_range"} (cw == 0: mono) --------------------------------------------
+def chroma_size(chroma, W, H):
+    """(cw, ch) of "444" / "422" / "420" / "mono" """
+    return {"444": (W, H), "422": ((W + 1) // 2, H), "420": ((W + 1) // 2, (H + 1) // 2), "mono": (0, 0)}[chroma]
+
+
+def record_bytes(fmt):
+    return (2 if fmt["depth"] > 8 else 1) * (fmt["W"] * fmt["H"] + 2 * fmt["cw"] * fmt["ch"])
+
+
+def split_record(rec, fmt):
+    """(Y [H,W], U [ch,cw] | None, V | None): views of a stored record (uint8 bytes), samples as stored"""
+    W, H, cw, ch = fmt["W"], fmt["H"], fmt["cw"], fmt["ch"]
+    a = np.frombuffer(rec, dtype=np.uint8, count=record_bytes(fmt)).view(np.uint8 if fmt["depth"] == 8 else np.dtype("<u2"))
+    y = a[: W * H].reshape(H, W)
+    if cw == 0:
+        return y, None, None
+    return y, a[W * H: W * H + cw * ch].reshape(ch, cw), a[W * H + cw * ch:].reshape(ch, cw)
+
+
+def _up(p, fmt):
+    """nearest chroma up-sampling to the luma grid"""
+    W, H = fmt["W"], fmt["H"]
+    if p.shape == (H, W):
+        return p
+    ry, rx = (1 if fmt["ch"] == H else 2), (1 if fmt["cw"] == W else 2)
+    return np.repeat(np.repeat(p, ry, axis=0), rx, axis=1)[:H, :W]
+
+
+def _blocks(p, fmt, pad_mode="edge"):
+    """[ch, cw, ry*rx]: the pixels of every chroma block, edge pixels repeated for odd sizes"""
+    W, H, cw, ch = fmt["W"], fmt["H"], fmt["cw"], fmt["ch"]
+    ry, rx = (1 if ch == H else 2), (1 if cw == W else 2)
+    p = np.pad(p, ((0, ch * ry - H), (0, cw * rx - W)), mode=pad_mode)
+    return p.reshape(ch, ry, cw, rx).transpose(0, 2, 1, 3).reshape(ch, cw, ry * rx)
+
+
+def _block_mean(p, fmt):
+    """the writer's sub-sampler: rounded mean of the block ((a + b + 1) >> 1, (a + b + c + d + 2) >> 2)"""
+    b = _blocks(p.astype(np.int32), fmt)
+    n = b.shape[2]
+    return ((b.sum(axis=2) + (n >> 1)) >> (n.bit_length() - 1)).astype(p.dtype)
+
+
+def decode_record(rec, fmt):
+    """the reader's statement: stored record -> uint8 BGR [H,W,3]"""
+    y, u, v = split_record(rec, fmt)
+    if u is None:
+        mid = np.full_like(y, 128 << (fmt["depth"] - 8))
+        return np.repeat(_yuv_to_bgr(y, mid, mid, fmt["full_range"], fmt["depth"])[..., :1], 3, axis=2)
+    return _yuv_to_bgr(y, _up(u, fmt), _up(v, fmt), fmt["full_range"], fmt["depth"])
+
+
+def _join(y, u, v):
+    parts = [y] if u is None else [y, u, v]
+    return np.concatenate([np.ascontiguousarray(p).reshape(-1).view(np.uint8) for p in parts])
+
+
+def encode_frame(frame, fmt):
+    """the writer's plain statement: uint8 BGR [H,W,3] -> stored record (uint8 bytes)"""
+    y, u, v = _bgr_to_yuv(frame, fmt["full_range"], fmt["depth"])
+    if fmt["cw"] == 0:
+        return _join(y, None, None)
+    return _join(y, _block_mean(u, fmt), _block_mean(v, fmt))
+
+
+def keep_record(src, frame, fmt):
+    """THE KEEP RULE (the definition; csrc/io_kernels.hip k_io_bgr_to_planes<KEEP> equals it bit for bit): a luma sample whose pixel
+    decodes from the source record to exactly the frame's colour is copied from the source; so is a chroma sample when every real pixel
+    of its block does; everything else is encoded from the frame.  src: the stored source record, frame: the final uint8 BGR frame."""
+    ys, us, vs = split_record(src, fmt)
+    same = np.all(decode_record(src, fmt) == frame, axis=-1)
+    ye, ue, ve = _bgr_to_yuv(frame, fmt["full_range"], fmt["depth"])
+    y = np.where(same, ys, ye)
+    if us is None:
+        return _join(y, None, None)
+    blk = _blocks(same, fmt).all(axis=2)
+    return _join(y, np.where(blk, us, _block_mean(ue, fmt)), np.where(blk, vs, _block_mean(ve, fmt)))
+
+
+# ---- the two device calls every resident loop makes (they differ in buffer names only) ------------------------------------------------
+def device_planes_to_bgr(rf, planes_ptr, H, W, bgr_ptr, n, stream_ptr):
+    """stored records at planes_ptr (format rf = a reader's planes_format()) -> uint8 BGR [n,H,W,3] at bgr_ptr, on the device"""
+    import ctypes as C
+
+    from ..._lib import check, lib
+
+    P = C.c_void_p
+    if rf.get("depth", 8) == 8:
+        check(lib.vsr_io_yuv_to_bgr(P(planes_ptr), rf["frame_bytes"], H, W, rf["cw"], rf["ch"], int(bool(rf["full_range"])), P(bgr_ptr), n, P(stream_ptr)))
     else:
-        y = ((16829 * r + 33039 * g + 6416 * b + 32768) >> 16) + 16
-        u = ((-9714 * r - 19070 * g + 28784 * b + 32768) >> 16) + 128
-        v = ((28784 * r - 24103 * g - 4681 * b + 32768) >> 16) + 128
-    return (np.clip(p, 0, 255).astype(np.uint8) for p in (y, u, v))
+        check(lib.vsr_io_planes_to_bgr(P(planes_ptr), rf["frame_bytes"], H, W, rf["cw"], rf["ch"], rf["depth"], int(bool(rf["full_range"])),
+                                       P(bgr_ptr), n, P(stream_ptr)))
+
+
+def device_bgr_to_planes(wf, bgr_ptr, H, W, planes_ptr, n, stream_ptr, src_ptr=None, src_fmt=None, path="this loop"):
+    """uint8 BGR [n,H,W,3] at bgr_ptr -> records of the writer's format wf (its planes_format()) at planes_ptr.  A writer that keeps
+    untouched samples (wf["keep"]) needs the frames' source records on the device as well (src_ptr, their format src_fmt): a loop that
+    has none must not write a differently made file in silence."""
+    import ctypes as C
+
+    from ..._lib import check, lib
+
+    P = C.c_void_p
+    if wf.get("keep"):
+        if src_ptr is None or src_fmt is None:
+            raise RuntimeError(f"VSR_Y4M_OUT=source: {path} does not carry the source planes to its store")
+        if any(src_fmt.get(k, 8 if k == "depth" else None) != wf[k] for k in ("frame_bytes", "cw", "ch", "depth", "full_range")):
+            raise RuntimeError(f"VSR_Y4M_OUT=source: {path} reads {src_fmt} but the sink was opened like {wf}")
+    elif wf.get("depth", 8) == 8 and wf.get("chroma", "444") in ("444", "420"):      # the default sink: the kernel and the bytes of old
+        check(lib.vsr_io_bgr_to_yuv(P(bgr_ptr), H, W, int(bool(wf["subsample_420"])), int(bool(wf["full_range"])), P(planes_ptr),
+                                    wf["frame_bytes"], n, P(stream_ptr)))
+        return
+    check(lib.vsr_io_bgr_to_planes(P(bgr_ptr), H, W, wf["cw"], wf["ch"], wf["depth"], int(bool(wf["full_range"])),
+                                   P(src_ptr) if wf.get("keep") else None, wf["frame_bytes"] if wf.get("keep") else 0, P(planes_ptr),
+                                   wf["frame_bytes"], n, P(stream_ptr)))
+
+
+def y4m_out_mode():
+    """VSR_Y4M_OUT: "444" (default: the 8-bit 4:4:4 studio-range sink) or "source" (the source's own format, untouched samples kept)"""
+    mode = os.environ.get("VSR_Y4M_OUT", "444")
+    if mode not in ("444", "source"):
+        raise RuntimeError(f"VSR_Y4M_OUT={mode}: expected 444 or source")
+    return mode
 
 
 def _device_color_enabled():
@@ -244,31 +389,50 @@ class _DeviceColor:
         """pinned host frames [batch][H][W][3]: where the writer collects frames / where to_bgr leaves converted ones"""
         return self.pin_bgr.numpy()
 
-    def to_bgr(self, n, cw, ch, full_range):
+    def to_bgr(self, n, cw, ch, full_range, depth=8):
         """the first n records of planes_buffer() -> the first n frames of bgr_buffer()"""
         t = self.torch
+        rf = {"frame_bytes": self.frame_bytes, "cw": cw, "ch": ch, "full_range": full_range, "depth": depth}
         with t.cuda.stream(self.stream):
             self.d_planes[:n].copy_(self.pin_planes[:n], non_blocking=True)
-            self.check(self.lib.vsr_io_yuv_to_bgr(self._p(self.d_planes), self.frame_bytes, self.H, self.W, cw, ch, int(bool(full_range)),
-                                                  self._p(self.d_bgr), n, self.C.c_void_p(self.stream.cuda_stream)))
+            device_planes_to_bgr(rf, self.d_planes.data_ptr(), self.H, self.W, self.d_bgr.data_ptr(), n, self.stream.cuda_stream)
             self.pin_bgr[:n].copy_(self.d_bgr[:n], non_blocking=True)
         self.stream.synchronize()
         return self.pin_bgr.numpy()[:n]
 
-    def from_bgr(self, n, subsample_420, full_range):
-        """the first n frames of bgr_buffer() -> the first n records of planes_buffer()"""
+    def source_buffer(self):
+        """pinned host records [batch][frame_bytes] of a keeping writer: the source records of the frames in bgr_buffer()"""
+        if getattr(self, "pin_src", None) is None:
+            self.pin_src = self.torch.empty((self.batch, self.frame_bytes), dtype=self.torch.uint8).pin_memory()
+            with self.torch.cuda.stream(self.stream):
+                self.d_src = self.torch.empty((self.batch, self.frame_bytes), dtype=self.torch.uint8, device=self.dev)
+        return self.pin_src.numpy()
+
+    def from_bgr(self, n, subsample_420, full_range, fmt=None, n_src=0):
+        """the first n frames of bgr_buffer() -> the first n records of planes_buffer().  fmt: a writer's planes_format() (else 8-bit
+        4:4:4 / 4:2:0); with fmt["keep"] the first n_src frames go with the records of source_buffer() (the rest is plainly encoded)"""
         t = self.torch
+        if fmt is None:
+            fmt = {"frame_bytes": self.frame_bytes, "subsample_420": subsample_420, "full_range": full_range}
+        plain = dict(fmt, keep=False)
+        st = self.stream.cuda_stream
         with t.cuda.stream(self.stream):
             self.d_bgr[:n].copy_(self.pin_bgr[:n], non_blocking=True)
-            self.check(self.lib.vsr_io_bgr_to_yuv(self._p(self.d_bgr), self.H, self.W, int(bool(subsample_420)), int(bool(full_range)),
-                                                  self._p(self.d_planes), self.frame_bytes, n, self.C.c_void_p(self.stream.cuda_stream)))
+            k = min(n, n_src) if fmt.get("keep") else 0
+            if k:
+                self.d_src[:k].copy_(self.pin_src[:k], non_blocking=True)
+                device_bgr_to_planes(fmt, self.d_bgr.data_ptr(), self.H, self.W, self.d_planes.data_ptr(), k, st, self.d_src.data_ptr(),
+                                     src_fmt=fmt)
+            if n > k:
+                device_bgr_to_planes(plain, self.d_bgr[k:].data_ptr(), self.H, self.W, self.d_planes[k:].data_ptr(), n - k, st)
             self.pin_planes[:n].copy_(self.d_planes[:n], non_blocking=True)
         self.stream.synchronize()
         return self.pin_planes.numpy()[:n]
 
 
 class Y4mVideo:
-    """YUV4MPEG2 reader: 8-bit C420* / C422 / C444 / Cmono, progressive; frames come out as BGR (BT.601)."""
+    """YUV4MPEG2 reader: C420* / C422 / C444 / Cmono at 8 bits, C420p10 / C422p10 / C444p10 / Cmono10 and the same with 12 (16-bit
+    little-endian samples), progressive; frames come out as 8-bit BGR (BT.601)."""
 
     def __init__(self, path):
         self.path = path
@@ -290,22 +454,29 @@ class Y4mVideo:
             elif t[0] == "C":
                 self.chroma = t[1:]
             elif t[0] == "I" and t[1:] not in ("p", "?"):
-                raise RuntimeError(f"{path}: interlaced y4m ({t}) is not supported")
-        if self.chroma.startswith("420"):
+                raise RuntimeError(f"{path}: interlaced y4m ({t}) is not supported (progressive streams are)")
+        self.header = head                            # the stream-header line as stored (a writer opened `like` this file repeats it)
+        supported = "420* / 422 / 444 / mono at 8 bits, 420 / 422 / 444 p10 and p12, mono10, mono12"
+        self.depth, kind = 8, self.chroma
+        deep = re.fullmatch(r"(420|422|444)p(\d+)|(mono)(\d+)", self.chroma)
+        if deep is not None:
+            kind, self.depth = deep.group(1) or deep.group(3), int(deep.group(2) or deep.group(4))
+            if self.depth not in (10, 12):
+                raise RuntimeError(f"{path}: {self.depth}-bit y4m (C{self.chroma}) is not supported ({supported})")
+        if kind.startswith("420"):
             self.cw, self.ch = (self.w + 1) // 2, (self.h + 1) // 2
-        elif self.chroma.startswith("422"):
+        elif kind == "422":
             self.cw, self.ch = (self.w + 1) // 2, self.h
-        elif self.chroma.startswith("444"):
+        elif kind == "444":
             self.cw, self.ch = self.w, self.h
-        elif self.chroma == "mono":
+        elif kind == "mono":
             self.cw = self.ch = 0
         else:
-            raise RuntimeError(f"{path}: chroma format C{self.chroma} is not supported (8-bit 420 / 422 / 444 / mono)")
-        if any(s in self.chroma for s in ("p10", "p12", "p14", "p16")):
-            raise RuntimeError(f"{path}: only 8-bit y4m is supported")
+            raise RuntimeError(f"{path}: chroma format C{self.chroma} is not supported ({supported})")
         self.full_range = b"XCOLORRANGE=FULL" in head
         self._data0 = self._f.tell()
-        self._fsize = self.w * self.h + 2 * self.cw * self.ch
+        self.fmt = {"W": self.w, "H": self.h, "cw": self.cw, "ch": self.ch, "depth": self.depth, "full_range": self.full_range}
+        self._fsize = record_bytes(self.fmt)
         self._count = None
         self._dc_args = (self.h, self.w, self._fsize) if _device_color_enabled() else None     # the converter is built on first use
         self._dc_obj = None
@@ -343,7 +514,7 @@ class Y4mVideo:
                 n = self.read_planes_into(self._dc.planes_buffer())
                 if n == 0:
                     return False, None
-                bgr = self._dc.to_bgr(n, self.cw, self.ch, self.full_range)
+                bgr = self._dc.to_bgr(n, self.cw, self.ch, self.full_range, self.depth)
                 self._ready = [bgr[k].copy() for k in range(n - 1, -1, -1)]       # frames of their own: the plugins patch rows into them
             return True, self._ready.pop()
         line = self._f.readline()
@@ -352,18 +523,7 @@ class Y4mVideo:
         buf = self._f.read(self._fsize)
         if len(buf) < self._fsize:
             return False, None
-        a = np.frombuffer(buf, dtype=np.uint8)
-        y = a[: self.w * self.h].reshape(self.h, self.w)
-        if self.cw == 0:
-            return True, np.repeat(_yuv_to_bgr(y, np.full_like(y, 128), np.full_like(y, 128), self.full_range)[..., :1], 3, axis=2)
-        n = self.cw * self.ch
-        u = a[self.w * self.h: self.w * self.h + n].reshape(self.ch, self.cw)
-        v = a[self.w * self.h + n:].reshape(self.ch, self.cw)
-        if (self.ch, self.cw) != (self.h, self.w):    # nearest chroma up-sampling
-            ry, rx = (1 if self.ch == self.h else 2), (1 if self.cw == self.w else 2)
-            u = np.repeat(np.repeat(u, ry, axis=0), rx, axis=1)[: self.h, : self.w]
-            v = np.repeat(np.repeat(v, ry, axis=0), rx, axis=1)[: self.h, : self.w]
-        return True, _yuv_to_bgr(y, u, v, self.full_range)
+        return True, decode_record(buf, self.fmt)     # nearest chroma up-sampling
 
     # raw access for the device-resident chunk loop (STTNAutoInpaint._run): the planes travel as stored, the GPU converts
     def planes_format(self):
@@ -372,7 +532,7 @@ class Y4mVideo:
             return None
         if self._ready:
             raise RuntimeError("read() and read_planes_into() cannot be mixed on one reader")
-        return {"frame_bytes": self._fsize, "cw": self.cw, "ch": self.ch, "full_range": self.full_range}
+        return {"frame_bytes": self._fsize, "cw": self.cw, "ch": self.ch, "full_range": self.full_range, "depth": self.depth}
 
     def record_layout(self):
         """{path, data_offset, prefix, frame_bytes, count} when every frame of the file is one fixed-size record (no per-frame parameters):
@@ -393,23 +553,53 @@ class Y4mVideo:
             k += 1
         return k
 
+    def skip_records(self, n):
+        """pass over the next n stored frames"""
+        for _ in range(n):
+            if not self._f.readline().startswith(b"FRAME"):
+                break
+            self._f.seek(self._fsize, 1)
+
     def release(self):
         self._f.close()
 
 
 class Y4mWriter:
-    """YUV4MPEG2 writer, 8-bit, BT.601 studio range; chroma "444" (default: no sub-sampling loss) or "420"."""
+    """YUV4MPEG2 writer, BT.601.  By default 8-bit studio range, chroma "444" (no sub-sampling loss) or "420"; also "422" / "mono",
+    depth 10 / 12 (16-bit little-endian samples) and full range.
 
-    def __init__(self, path, fps, size, chroma="444"):
+    like=<path of a *.y4m source>: the SOURCE'S OWN FORMAT.  Its stream-header line is written verbatim, frame k written through
+    write() is paired with record k of the source (read through a handle of this writer's own, in order), and the output record is
+    made by the keep rule (keep_record): samples whose decoded colour did not change are copied, not re-encoded.  A run that changes
+    nothing writes its input back byte for byte.  A source record that is missing falls back to plain encoding."""
+
+    def __init__(self, path, fps, size, chroma="444", depth=8, full_range=False, like=None):
         self.w, self.h = int(size[0]), int(size[1])
+        self._src = None
+        if like is not None:
+            self._src = Y4mVideo(os.fspath(like))
+            if (self._src.w, self._src.h) != (self.w, self.h):
+                self._src.release()
+                raise RuntimeError(f"{path}: a sink of {self.w}x{self.h} cannot be written like {like} ({self._src.w}x{self._src.h})")
+            self.fmt = dict(self._src.fmt)
+            chroma = {(self.w, self.h): "444", ((self.w + 1) // 2, self.h): "422", (0, 0): "mono"}.get((self.fmt["cw"], self.fmt["ch"]), "420")
+            header = self._src.header
+        else:
+            if chroma not in ("444", "422", "420", "mono") or depth not in DEPTHS:
+                raise ValueError(f"Y4mWriter: chroma {chroma!r} / depth {depth!r}: expected 444 / 422 / 420 / mono and {DEPTHS}")
+            cw, ch = chroma_size(chroma, self.w, self.h)
+            self.fmt = {"W": self.w, "H": self.h, "cw": cw, "ch": ch, "depth": int(depth), "full_range": bool(full_range)}
+            num, den = (int(round(fps * 1001)), 1001) if abs(fps - round(fps)) > 1e-3 else (int(round(fps)), 1)
+            tag = {"444": "444", "420": "420mpeg2", "422": "422", "mono": "mono"}[chroma]
+            if depth > 8:
+                tag = f"mono{depth}" if chroma == "mono" else f"{chroma}p{depth}"
+            header = f"YUV4MPEG2 W{self.w} H{self.h} F{num}:{den} Ip A1:1 C{tag} XCOLORRANGE={'FULL' if full_range else 'LIMITED'}\n".encode()
         self.chroma = chroma
-        num, den = (int(round(fps * 1001)), 1001) if abs(fps - round(fps)) > 1e-3 else (int(round(fps)), 1)
+        self._plain = like is None and self.fmt["depth"] == 8 and not self.fmt["full_range"] and chroma in ("444", "420")
         self._f = open(path, "wb", buffering=1 << 22)
-        tag = "444" if chroma == "444" else "420mpeg2"
-        self._f.write(f"YUV4MPEG2 W{self.w} H{self.h} F{num}:{den} Ip A1:1 C{tag} XCOLORRANGE=LIMITED\n".encode())
+        self._f.write(header)
         self._header_bytes = self._f.tell()
-        cw, ch = (self.w, self.h) if chroma == "444" else ((self.w + 1) // 2, (self.h + 1) // 2)
-        self._dc_args = (self.h, self.w, self.w * self.h + 2 * cw * ch) if _device_color_enabled() else None
+        self._dc_args = (self.h, self.w, record_bytes(self.fmt)) if _device_color_enabled() else None
         self._dc_obj = None
         self._pending = 0
 
@@ -419,10 +609,19 @@ class Y4mWriter:
             self._dc_obj = _DeviceColor(*self._dc_args)
         return self._dc_obj
 
+    def _format(self):
+        return {"frame_bytes": record_bytes(self.fmt), "subsample_420": self.chroma == "420", "full_range": self.fmt["full_range"],
+                "cw": self.fmt["cw"], "ch": self.fmt["ch"], "depth": self.fmt["depth"], "chroma": self.chroma, "keep": self._src is not None}
+
     def _flush(self):
         if self._pending:
             n, self._pending = self._pending, 0
-            self.write_planes(self._dc.from_bgr(n, self.chroma != "444", False))
+            if self._plain:
+                recs = self._dc.from_bgr(n, self.chroma != "444", False)
+            else:
+                k = self._src.read_planes_into(self._dc.source_buffer()[:n]) if self._src is not None else 0
+                recs = self._dc.from_bgr(n, False, False, fmt=self._format(), n_src=k)
+            self._write_records(recs)
 
     def write(self, frame):
         if frame.dtype != np.uint8:
@@ -433,31 +632,33 @@ class Y4mWriter:
             if self._pending == self._dc.batch:
                 self._flush()
             return
-        y, u, v = _bgr_to_yuv(frame, False)
-        if self.chroma != "444":
-            h2, w2 = (self.h + 1) // 2 * 2, (self.w + 1) // 2 * 2
-            def sub(p):
-                p = np.pad(p, ((0, h2 - self.h), (0, w2 - self.w)), mode="edge").astype(np.uint16)
-                return ((p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + 2) >> 2).astype(np.uint8)
-            u, v = sub(u), sub(v)
         self._f.write(b"FRAME\n")
-        self._f.write(y.tobytes())
-        self._f.write(u.tobytes())
-        self._f.write(v.tobytes())
+        if self._src is not None:
+            rec = np.empty((1, record_bytes(self.fmt)), np.uint8)
+            if self._src.read_planes_into(rec) == 1:
+                self._f.write(keep_record(rec[0], frame, self.fmt).tobytes())
+                return
+        self._f.write(encode_frame(frame, self.fmt).tobytes())
 
     def planes_format(self):
-        """None without a GPU; else what write_planes expects per frame (BT.601 studio range)"""
+        """None without a GPU; else what write_planes expects per frame.  "keep": this writer pairs frames with the records of a
+        source (like=...): whoever converts on the device applies the keep rule with those records (device_bgr_to_planes)."""
         if self._dc_args is None:
             return None
-        return {"frame_bytes": self._dc_args[2], "subsample_420": self.chroma != "444", "full_range": False}
+        return self._format()
 
-    def write_planes(self, recs):
-        """frames already converted on the device: uint8 [n][frame_bytes]"""
-        if self._pending:
-            self._flush()
+    def _write_records(self, recs):
         for rec in recs:
             self._f.write(b"FRAME\n")
             self._f.write(rec)
+
+    def write_planes(self, recs):
+        """frames already converted on the device: uint8 [n][frame_bytes] (by the keep rule, when this writer keeps)"""
+        if self._pending:
+            self._flush()
+        if self._src is not None:
+            self._src.skip_records(len(recs))         # the pairing of write() goes on behind them
+        self._write_records(recs)
 
     def record_layout(self, count):
         """For tools/rank_io.py: the header goes to disk, the file is grown to its final size of `count` frames, and the layout of its
@@ -472,6 +673,8 @@ class Y4mWriter:
     def release(self):
         if self._dc_obj is not None:
             self._flush()
+        if self._src is not None:
+            self._src.release()
         self._f.close()
 
 
@@ -804,16 +1007,16 @@ def open_video(video):
                            f"*.npy) and in-memory ArrayVideo clips need neither") from e
 
 
-def open_writer(path, fps, size, frames=None):
+def open_writer(path, fps, size, frames=None, like=None):
     """Sink for `path` (size = (W, H)); raises when nothing on this machine can write that container -- never a silent
-    in-memory fallback for a file the caller asked for."""
+    in-memory fallback for a file the caller asked for.  like: a *.y4m source whose format a *.y4m sink takes (Y4mWriter)."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     if ext == ".npy":
         return NpyWriter(path, fps, size, capacity=frames)
     if ext == ".y4m":
-        return Y4mWriter(path, fps, size)
+        return Y4mWriter(path, fps, size, like=like)
     if ext in IMAGE_EXTS:
         return ImageWriter(path)
     if ffmpeg_path() is not None:
