@@ -123,7 +123,9 @@ def main():
     ap.add_argument("--precision", default=None, help="propainter: f32 (default) or split")
     ap.add_argument("--det-program", default="ppocr_det_graph.json", help="detector program fixture under tests/golden (server: ppocr_det_graph.json, "
                                                                           "mobile: ppocr_det_fast_graph.json)")
-    ap.add_argument("--resident", default="1", choices=["0", "1"], help="0: force the host-frame loop")
+    ap.add_argument("--resident", default="1", choices=["0", "1", "windows"],
+                    help="0: force the host-frame loop; windows: a clip over --resident-gb runs as HBM-resident windows (VSR_IO_RESIDENT)")
+    ap.add_argument("--resident-gb", type=float, default=None, help="VSR_RESIDENT_GB for this run (default: the environment's, else 64)")
     ap.add_argument("--always-on", action="store_true", help="subtitle on every frame: ONE interval, i.e. the batch sizes batch_generator makes of "
                                                              "the whole clip (1200 frames -> 17 x 68 + 44 for propainter, 25 x 47 + 25 for sttn-det / lama)")
     ap.add_argument("--keep", action="store_true")
@@ -133,6 +135,8 @@ def main():
     assert torch.cuda.is_available(), "bench_e2e.py needs a GPU"
     H, W, box = RES[args.res]
     os.environ["VSR_IO_RESIDENT"] = args.resident
+    if args.resident_gb is not None:
+        os.environ["VSR_RESIDENT_GB"] = repr(args.resident_gb)
     tmp = tempfile.mkdtemp(prefix="vsr_e2e_")
     src, dst = args.clip or os.path.join(tmp, "in.y4m"), os.path.join(tmp, "out.y4m")
     # subtitle on screen 100 frames out of every 120 (ten intervals in 1200 frames)
@@ -187,7 +191,11 @@ def main():
                         "frames_with_text": det.total("positives"), "lanes": len(det._family),
                         "frames_per_forward": det.batch_size, "postprocess_host_fallbacks": post.host_fallbacks if post is not None else None,
                         "map": "injected at the graph output (synthetic weights find no text); forward executed in full"},
-           "frames_written": out_frames, "resident": args.resident == "1",
+           "frames_written": out_frames, "resident": args.resident == "1" if args.resident != "windows" else "windows",
+           "resident_gb": float(os.environ.get("VSR_RESIDENT_GB", "64")),
+           "resident_windows": ({"windows": len(sr.resident_windows["windows"]), "bytes_max": sr.resident_windows["bytes_max"],
+                                 "records_read_pass_a": sr.resident_windows["records_read_pass_a"]}
+                                if getattr(sr, "resident_windows", None) is not None else None),
            "batch_lanes": int(os.environ.get("VSR_BATCH_LANES", "1")), "sttn_window_lanes": int(os.environ.get("VSR_STTN_LANES", "2")),
            "precision": os.environ.get("VSR_PP_PRECISION", "f32") if args.mode == "propainter" else "f32",
            "clip": f"synthetic {W}x{H} y4m 4:2:0, subtitle on {'every frame' if args.always_on else '100 of every 120 frames'} in box {box}; "

@@ -62,6 +62,7 @@ class SubtitleRemover:
         self.progress_total = 0
         self.isFinished = False
         self.phase_seconds = {}
+        self.resident_windows = None             # what a windowed run did (tools/resident_windows.WindowedClip.report); None: no such run
 
     @property
     def video_writer(self):
@@ -163,6 +164,58 @@ class SubtitleRemover:
         finally:
             reader.release()
 
+    def _open_windowed(self):
+        """tools/resident_windows.WindowedClip when VSR_IO_RESIDENT=windows (--resident-windows) and this run could keep its video in HBM
+        but for the size of the clip; None otherwise (and for a clip that fits: _open_resident took it)"""
+        from .tools import resident_windows
+        from .tools.resident import ResidentClip
+
+        if not resident_windows.enabled() or self._distributed() is not None or getattr(self, "gui_mode", False) or not self.is_path:
+            return None
+        reader = open_video(self.video_path)
+        try:
+            fmts = ResidentClip.formats(reader, self.video_writer)
+            info = reader.info()
+            if fmts is None or ResidentClip.fits(info["len"], info["H_ori"], info["W_ori"], fmts[0]["frame_bytes"] if fmts[1].get("keep") else 0):
+                return None
+            # (the frames a resident clip would hold after loading: a last record cut short is not one of them)
+            n = reader.whole_records() if hasattr(reader, "whole_records") else info["len"]
+            return resident_windows.WindowedClip(self.video_path, fmts[0], fmts[1], n, info["H_ori"], info["W_ori"], self.device)
+        finally:
+            reader.release()
+
+    def _windows_do_not_fit(self, why):
+        self.append_output(f"resident windows: {why} does not fit half of VSR_RESIDENT_GB; taking the host-frame loop")
+
+    def _run_windowed(self, wclip, jobs, plugin, tbar, singles=(), single_frame_inpaint=None):
+        """pass B of a windowed run (tools/resident_windows.py): jobs [(lo, hi, mask)] and singles [(frame, mask)] index the file; every
+        window is inpainted in place like a resident clip and stored as its frames become final.  False: a batch does not fit, nothing
+        was written -- the caller takes the host-frame loop."""
+        import torch
+
+        from .tools.resident_windows import WindowsDoNotFit
+
+        try:
+            windows = wclip.plan_pass_b(jobs)
+        except WindowsDoNotFit as e:
+            self._windows_do_not_fit(e)
+            self.resident_windows = None           # (pass A ran in windows; the run as a whole does not)
+            return False
+
+        def work(win):
+            lo, hi = win.lo, win.lo + len(win)
+            for at, mask in singles:                                                   # main.py:217-224: LamaInpaint.inpaint on the whole frame
+                if lo <= at < hi:
+                    one = single_frame_inpaint(win.frames[at - lo].cpu().numpy(), mask)
+                    win.frames[at - lo].copy_(torch.from_numpy(np.ascontiguousarray(one)))
+            mine = [(win.frames[max(a, lo) - lo:min(b, hi) - lo], mask) for a, b, mask in jobs if a < hi and b > lo]
+            self._run_resident_jobs(mine, plugin, win, win.store)
+
+        t0 = time.time()
+        wclip.run_pass_b(windows, self.video_writer, lambda: self.update_progress(tbar, increment=1), work)
+        self.phase_seconds["windows, pass B: read + upload + YUV->BGR, inpainting, BGR->YUV + download + write"] = time.time() - t0
+        return True
+
     def _run_resident_jobs(self, jobs, plugin, clip, store=None):
         """the independent batches of a resident run: one after the other, or over VSR_BATCH_LANES plugin instances (tools/batch_lanes.py).
         store: a tools/resident.StreamingStore -- with one lane the frames in front of the next batch are handed to it as each batch
@@ -187,6 +240,21 @@ class SubtitleRemover:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))
             store.ready(first[j + 1] if j + 1 < len(jobs) else len(clip), ev)
+
+    def _find_subtitles(self, detector, clip, wclip):
+        """the detector pass -> (sub_list, wclip): over the resident clip, over the file in windows (pass A; a detector batch that does
+        not fit sends the run to the host-frame loop: wclip comes back None), or over host frames"""
+        if wclip is not None:
+            from .tools.resident_windows import WindowsDoNotFit
+
+            name = "windows, pass A: read + upload + YUV->BGR, detector pass" + (", scene cuts" if wclip.want_scene_cuts else "")
+            try:
+                sub_list = self._timed(name, detector.find_subtitle_frame_no, sub_remover=self, clip=wclip)
+                self.resident_windows = wclip.report
+                return sub_list, wclip
+            except WindowsDoNotFit as e:
+                self._windows_do_not_fit(e)
+        return self._timed("detector pass", detector.find_subtitle_frame_no, sub_remover=self, **self._clip_kw(clip)), None
 
     @staticmethod
     def _clip_kw(clip):
@@ -227,9 +295,13 @@ class SubtitleRemover:
         # sttn-det inpainting does not care) -- the second instance's streams stay alive beside the plugin's
         detector.det_lanes_default = 1
         # the clip stays in HBM only for a plugin that takes device tensors (an injected callable, or the cv2 plugin, gets host frames)
-        resident = self._open_resident() if getattr(propainter_inpaint, "accepts_device_frames", False) else None
+        on_device = getattr(propainter_inpaint, "accepts_device_frames", False)
+        resident = self._open_resident() if on_device else None
         clip = resident[0] if resident is not None else None
-        sub_list = self._timed("detector pass", detector.find_subtitle_frame_no, sub_remover=self, **self._clip_kw(clip))
+        wclip = self._open_windowed() if on_device and resident is None else None
+        if wclip is not None:
+            wclip.want_scene_cuts = scene_div_points is None       # pass A is the one walk over every frame: the scene kernels ride along
+        sub_list, wclip = self._find_subtitles(detector, clip, wclip)
         if len(sub_list) == 0:
             self._run_items(tbar, (), propainter_inpaint)                  # releases the peers before failing
             raise Exception(f"No subtitle detected in {self.video_path}")
@@ -237,40 +309,57 @@ class SubtitleRemover:
         if scene_div_points is None:                 # main.py:165: self.sub_detector.get_scene_div_frame_no(self.video_path)
             dev = self.device
             scene_div_points = self._timed("scene cuts", detector.get_scene_div_frame_no, self.video_path,
-                                           device=int(dev.split(":")[1]) if isinstance(dev, str) and ":" in dev else 0, **self._clip_kw(clip))
+                                           device=int(dev.split(":")[1]) if isinstance(dev, str) and ":" in dev else 0,
+                                           **self._clip_kw(clip if wclip is None else wclip))
         ranges = detector.split_range_by_scene(ranges, list(scene_div_points))
+
+        def index_jobs(n, single):
+            """the walk of items() below over frame numbers alone -> [(lo, hi, mask)], 0-based, the batches of two frames and more;
+            single(frame, mask): an interval of one frame that LaMa takes"""
+            index, jobs = 0, []
+            while index < n:
+                index += 1
+                if index not in sub_list or not self.is_current_frame_no_start(index, ranges):
+                    continue
+                start_frame_no = index
+                end_frame_no = self.find_frame_no_end(index, ranges)
+                if end_frame_no == -1:
+                    continue
+                index = min(end_frame_no, n)
+                nos = list(range(start_frame_no - 1, index))                          # 0-based indices of the interval
+                mask = create_mask(self.mask_size, sub_list[start_frame_no])
+                for batch in ([nos] if len(nos) == 1 else batch_generator(nos, config.propainterMaxLoadNum.value)):
+                    if len(batch) == 1:
+                        if single_frame_inpaint is None:
+                            self.passed_through_single_frames += 1
+                            if self.passed_through_single_frames == 1:
+                                self.append_output("warning: no LaMa weights configured (LAMA_MODEL_PATH): isolated subtitle frames pass through")
+                        else:
+                            single(batch[0], mask)
+                    else:
+                        jobs.append((batch[0], batch[-1] + 1, mask))
+            return jobs
+
+        if wclip is not None:
+            # over the budget: the same batches, on windows of the file that follow each other through HBM (tools/resident_windows.py)
+            singles = []
+            jobs = index_jobs(wclip.n, lambda at, mask: singles.append((at, mask)))
+            if self._run_windowed(wclip, jobs, propainter_inpaint, tbar, singles, single_frame_inpaint):
+                return
+            self.passed_through_single_frames = 0                  # (the host-frame loop below counts them again)
         if resident is not None:
             # the same walk over frame numbers as items() below, on the clip in HBM: batches are slices inpainted in place
             import torch
 
             clip, wf = resident
-            n, index = len(clip), 0
-            jobs = []                              # (slice of the clip, mask): independent batches, run by tools/batch_lanes.py
+
+            def single(at, mask):                  # main.py:217-224: LamaInpaint.inpaint on the whole frame
+                one = single_frame_inpaint(clip.frames[at].cpu().numpy(), mask)
+                clip.frames[at].copy_(torch.from_numpy(np.ascontiguousarray(one)))
 
             def inpaint_all():
-                nonlocal index
-                while index < n:
-                    index += 1
-                    if index not in sub_list or not self.is_current_frame_no_start(index, ranges):
-                        continue
-                    start_frame_no = index
-                    end_frame_no = self.find_frame_no_end(index, ranges)
-                    if end_frame_no == -1:
-                        continue
-                    index = min(end_frame_no, n)
-                    nos = list(range(start_frame_no - 1, index))                          # 0-based indices of the interval
-                    mask = create_mask(self.mask_size, sub_list[start_frame_no])
-                    for batch in ([nos] if len(nos) == 1 else batch_generator(nos, config.propainterMaxLoadNum.value)):
-                        if len(batch) == 1:
-                            if single_frame_inpaint is None:
-                                self.passed_through_single_frames += 1
-                                if self.passed_through_single_frames == 1:
-                                    self.append_output("warning: no LaMa weights configured (LAMA_MODEL_PATH): isolated subtitle frames pass through")
-                            else:                                                          # main.py:217-224: LamaInpaint.inpaint on the whole frame
-                                one = single_frame_inpaint(clip.frames[batch[0]].cpu().numpy(), mask)
-                                clip.frames[batch[0]].copy_(torch.from_numpy(np.ascontiguousarray(one)))
-                        else:
-                            jobs.append((clip.frames[batch[0]:batch[-1] + 1], mask))
+                # (slice of the clip, mask): independent batches, run by tools/batch_lanes.py
+                jobs = [(clip.frames[lo:hi], mask) for lo, hi, mask in index_jobs(len(clip), single)]
                 self._run_resident_jobs(jobs, propainter_inpaint, clip, store)
 
             from .tools.resident import StreamingStore
@@ -331,9 +420,10 @@ class SubtitleRemover:
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), model)
         detector = SubtitleDetect(self.video_path, self.sub_areas, text_detector=text_detector)
-        resident = self._open_resident() if getattr(model, "accepts_device_frames", False) else None
-        sub_list = self._timed("detector pass", detector.find_subtitle_frame_no, sub_remover=self,
-                               **self._clip_kw(resident[0] if resident is not None else None))
+        on_device = getattr(model, "accepts_device_frames", False)
+        resident = self._open_resident() if on_device else None
+        wclip = self._open_windowed() if on_device and resident is None else None
+        sub_list, wclip = self._find_subtitles(detector, resident[0] if resident is not None else None, wclip)
         if len(sub_list) == 0:
             self._run_items(tbar, (), model)
             raise Exception(f"No subtitle detected in {self.video_path}")
@@ -354,23 +444,31 @@ class SubtitleRemover:
                         coords.append(area)
             return create_mask(self.mask_size, coords)
 
+        def index_jobs(n):
+            """the walk of items() below over frame numbers alone -> [(lo, hi, mask)], 0-based: the batches of a clip of n frames"""
+            idx, jobs = 0, []
+            while idx < n:
+                idx += 1
+                if idx not in start_end:
+                    continue
+                first, last = idx, start_end[idx]
+                idx = min(last, n)                                 # frames first .. idx are read (:300-305)
+                mask = interval_mask(first, last)
+                for batch in batch_generator(list(range(first - 1, idx)), config.getSttnMaxLoadNum()):
+                    if len(batch) >= 1:
+                        jobs.append((batch[0], batch[-1] + 1, mask))
+            return jobs
+
+        if wclip is not None:
+            # over the budget: the same batches, on windows of the file that follow each other through HBM (tools/resident_windows.py)
+            if self._run_windowed(wclip, index_jobs(wclip.n), model, tbar):
+                return
         if resident is not None:
             # the same walk over frame numbers as items() below, on the clip in HBM: a batch is a slice, inpainted in place
             clip, wf = resident
-            n = len(clip)
 
             def inpaint_all():
-                idx, jobs = 0, []
-                while idx < n:
-                    idx += 1
-                    if idx not in start_end:
-                        continue
-                    first, last = idx, start_end[idx]
-                    idx = min(last, n)                             # frames first .. idx are read (:300-305)
-                    mask = interval_mask(first, last)
-                    for batch in batch_generator(list(range(first - 1, idx)), config.getSttnMaxLoadNum()):
-                        if len(batch) >= 1:
-                            jobs.append((clip.frames[batch[0]:batch[-1] + 1], mask))
+                jobs = [(clip.frames[lo:hi], mask) for lo, hi, mask in index_jobs(len(clip))]
                 self._run_resident_jobs(jobs, model, clip, store)
 
             from .tools.resident import StreamingStore
@@ -530,6 +628,8 @@ def main(argv=None):
     config.inpaintMode.value = args.inpaint_mode
     if args.y4m_out is not None:
         os.environ["VSR_Y4M_OUT"] = args.y4m_out
+    if args.resident_windows:
+        os.environ["VSR_IO_RESIDENT"] = "windows"
     sr = SubtitleRemover(args.input)
     sr.sub_areas = [tuple(c) for c in args.subtitle_area_coords]
     if args.output is not None:

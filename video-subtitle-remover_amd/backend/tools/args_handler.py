@@ -20,6 +20,9 @@ def build_parser():
     # not in the reference: what a *.y4m sink holds (overrides VSR_Y4M_OUT)
     parser.add_argument("--y4m-out", type=str, default=None, choices=["444", "source"],
                         help="*.y4m output: 444 = 8-bit 4:4:4 (default), source = the format of the *.y4m input, untouched samples kept")
+    # not in the reference: a clip over VSR_RESIDENT_GB stays on the GPU as a sequence of resident windows (sets VSR_IO_RESIDENT=windows)
+    parser.add_argument("--resident-windows", action="store_true",
+                        help="a *.y4m clip too large for VSR_RESIDENT_GB runs as HBM-resident windows instead of the host-frame loop")
     return parser
 
 

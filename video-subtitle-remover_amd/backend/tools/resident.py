@@ -10,12 +10,13 @@ sttn-auto only).
 
 Eligible: a raw planar source and sink whose colour conversion runs on the GPU (*.y4m, tools/video_io.py), one process, and a clip
 that fits VSR_RESIDENT_GB (default 64) as BGR.  Anything else keeps the host-frame loop; VSR_IO_RESIDENT=0 forces it.
+VSR_IO_RESIDENT=windows: a clip that does not fit runs as a sequence of resident windows instead (tools/resident_windows.py).
 """
 import os
 
 import torch
 
-from .video_io import device_bgr_to_planes, device_planes_to_bgr
+from .video_io import device_planes_to_bgr
 
 
 class ResidentClip:
@@ -75,32 +76,6 @@ class ResidentClip:
     def __len__(self):
         return int(self.frames.shape[0])
 
-    def store(self, writer, wf, lo, hi, tick=None):
-        """frames [lo, hi) -> the writer's planes, converted on the device, in order"""
-        dev = self.frames.device
-        n, H, W, _ = self.frames.shape
-        if getattr(self, "_store_bufs", None) is None or self._store_bufs[0] != wf["frame_bytes"]:      # (kept: store() may be called range by range)
-            self._store_bufs = (wf["frame_bytes"],
-                                [torch.empty((self.BATCH, wf["frame_bytes"]), dtype=torch.uint8).pin_memory() for _ in range(2)],
-                                [torch.empty((self.BATCH, wf["frame_bytes"]), dtype=torch.uint8, device=dev) for _ in range(2)])
-        _, pins, dout = self._store_bufs
-        b = 0
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev)
-            for s in range(lo, hi, self.BATCH):
-                k = min(self.BATCH, hi - s)
-                device_bgr_to_planes(wf, self.frames[s:].data_ptr(), H, W, dout[b].data_ptr(), k, stream.cuda_stream,
-                                     self.planes[s:].data_ptr() if self.planes is not None else None, self.fmt_in, path="the resident clip")
-                pins[b][:k].copy_(dout[b][:k], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(stream)
-                ev.synchronize()
-                writer.write_planes(pins[b].numpy()[:k])         # the writer thread takes its own copy
-                if tick is not None:
-                    for _ in range(k):
-                        tick()
-                b ^= 1
-
 
 class StreamingStore:
     """Writes the frames of a ResidentClip in order AS THEY BECOME FINAL, on its own thread and stream.
@@ -115,49 +90,20 @@ class StreamingStore:
         st.finish()              everything up to len(clip); joins the thread, re-raises its error"""
 
     def __init__(self, clip, writer, wf, tick=None):
-        import queue
-        import threading
+        from .resident_windows import Window, WindowStore
 
-        self.clip, self.writer, self.wf, self.tick = clip, writer, wf, tick
-        self._q = queue.Queue()
-        self._error = None
-        self._thread = threading.Thread(target=self._run, name="vsr-streaming-store", daemon=True)
-        self._thread.start()
-
-    def _run(self):
-        dev = self.clip.frames.device
-        lo = 0
-        with torch.cuda.device(dev), torch.cuda.stream(torch.cuda.Stream(dev)):
-            while True:
-                item = self._q.get()
-                if item is None:
-                    return
-                if self._error is not None:       # after a failed write: drain the queue until the sentinel, write nothing more
-                    continue
-                try:
-                    hi, event = item
-                    if event is not None:
-                        event.synchronize()
-                    hi = min(int(hi), len(self.clip))
-                    if hi > lo:
-                        self.clip.store(self.writer, self.wf, lo, hi, self.tick)
-                        lo = hi
-                except BaseException as e:        # noqa: BLE001 -- re-raised by ready() / finish() in the caller's thread
-                    self._error = e
+        # the whole clip as one window of tools/resident_windows.WindowStore: one conversion / download / write loop for both paths
+        _, H, W, _ = clip.frames.shape
+        self._win = Window(0, clip.frames, clip.planes, clip.fmt_in, None)
+        self._store = WindowStore(writer, wf, H, W, clip.frames.device, ResidentClip.BATCH, tick, name="vsr-streaming-store",
+                                  path="the resident clip")
 
     def ready(self, hi, event=None):
-        if self._error is not None:               # fail fast: do not inpaint the rest of the clip for a file that cannot be written
-            raise self._error
-        self._q.put((hi, event))
+        self._store.ready(self._win, hi, event)
 
     def abort(self):
         """the run failed: stop writing, release the thread"""
-        self._q.put(None)
-        self._thread.join()
+        self._store.abort()
 
     def finish(self):
-        self._q.put((len(self.clip), None))
-        self._q.put(None)
-        self._thread.join()
-        if self._error is not None:
-            raise self._error
+        self._store.finish(self._win)

@@ -124,24 +124,48 @@ class ContentDetector:
         return cuts
 
 
+class SceneStream:
+    """The clip= branch of get_scene_div_frame_no for frames that pass through HBM in pieces (tools/resident_windows.py, pass A):
+    feed() takes consecutive runs of frames in file order; device_batch carries the last frame across calls and its sums are
+    integers, so cuts() equals the resident pass whatever the pieces were."""
+
+    def __init__(self, H, W, device=0, detector=None):
+        self.det = detector if detector is not None else ContentDetector(device=device)
+        with torch.cuda.device(self.det.device):
+            _, w, h = self.det._buffers(H, W)[:3]
+        self.npix = h * w
+        self._out, self._have_prev = [], False
+
+    def feed(self, frames):
+        """frames: uint8 [n,H,W,3] BGR on the device, the frames that follow those of the last call"""
+        det = self.det
+        with torch.cuda.device(det.device):
+            for s in range(0, int(frames.shape[0]), det.batch_frames):
+                sums = det.device_batch(frames[s:s + det.batch_frames], self._have_prev)
+                if sums.shape[0]:
+                    self._out.append(sums.cpu().numpy().copy())
+                self._have_prev = True
+
+    def cuts(self):
+        """1-based numbers of the frames that start a new scene"""
+        sums = np.concatenate(self._out) if self._out else np.zeros((0, 3), np.int64)
+        return [c + 1 for c in self.det.process(sums, self.npix)]
+
+
 def get_scene_div_frame_no(video, device=0, detector=None, clip=None):
     """SubtitleDetect.get_scene_div_frame_no (subtitle_detect.py:158-170): `start.frame_num + 1` of every detected scene that
     does not start at frame 0.  `video`: a path or frame source accepted by video_io.open_video; clip: the same video resident in
     HBM (tools/resident.ResidentClip) -- the kernels then read it where it is, no third decoding pass."""
+    if clip is not None and getattr(clip, "windowed", False):
+        if clip.scene_cuts is None:
+            raise RuntimeError("the windowed pass over the file (SubtitleDetect._find_windowed) ran without want_scene_cuts")
+        return list(clip.scene_cuts)
     det = detector if detector is not None else ContentDetector(device=device)
     if clip is not None:
-        n, H, W, _ = clip.frames.shape
-        npix = None
-        out, have_prev = [], False
-        with torch.cuda.device(det.device):
-            _, w, h = det._buffers(H, W)[:3]
-            for s in range(0, n, det.batch_frames):
-                sums = det.device_batch(clip.frames[s:s + det.batch_frames], have_prev)
-                if sums.shape[0]:
-                    out.append(sums.cpu().numpy().copy())
-                have_prev = True
-        sums = np.concatenate(out) if out else np.zeros((0, 3), np.int64)
-        return [c + 1 for c in det.process(sums, h * w)]
+        _, H, W, _ = clip.frames.shape
+        stream = SceneStream(H, W, detector=det)
+        stream.feed(clip.frames)
+        return stream.cuts()
     reader = open_video(video)
     info = reader.info()
 

@@ -57,6 +57,8 @@ class SubtitleDetect:
         clip: the decoded video resident in HBM (tools/resident.ResidentClip): the sampled frames are taken from it instead of a
         second decoding pass over the file."""
         if clip is not None:
+            if getattr(clip, "windowed", False):      # over the budget: the same batches, window after window (tools/resident_windows.py)
+                return self._find_windowed(sub_remover, clip)
             return self._find_resident(sub_remover, clip)
         reader = open_video(self.video_path)
         sampled = {}
@@ -130,6 +132,86 @@ class SubtitleDetect:
                 boxes = self._keep_inside(res)
                 if len(boxes) > 0:
                     sampled[no] = boxes
+        return self.fill_and_unify(sampled)
+
+    def _find_windowed(self, sub_remover, wclip):
+        """_find_resident for a clip that passes through HBM in windows (tools/resident_windows.WindowedClip, pass A): the same sampled
+        numbers in the same parts of batch_size, each part gathered from the window that holds it and handed to the same detector
+        lanes.  When wclip.want_scene_cuts, every frame is read and also fed to the scene-cut kernels in frame order
+        (scene_detect.SceneStream); the cuts are left in wclip.scene_cuts."""
+        if self.text_detector is None:
+            raise RuntimeError("no text detector configured (PP-OCRv5 weights are not part of the reference mount)")
+        import contextlib
+
+        import torch
+
+        from . import batch_lanes
+
+        ab = sub_remover.ab_sections if sub_remover is not None else None
+        nos = [no for no in range(1, len(wclip) + 1)
+               if is_frame_number_in_ab_sections(no - 1, ab) and ((no - 1) % self.SAMPLE_STEP == 0 or self.SAMPLE_STEP <= 1)]
+        batch = max(1, getattr(self.text_detector, "batch_size", 1))
+        on_device = hasattr(self.text_detector, "predict_batch_device")
+        parts = [nos[s:s + batch] for s in range(0, len(nos), batch)]
+        units = wclip.plan_pass_a(parts)                   # (WindowsDoNotFit before any frame is read)
+        dev = torch.device(wclip.device)
+        if not hasattr(self, "_det_lanes"):
+            self._det_lanes = {}
+        detectors = batch_lanes.lane_plugins(self.text_detector,
+                                             batch_lanes.lanes_from_env("VSR_DET_LANES", getattr(self, "det_lanes_default", None)) if on_device else 1,
+                                             self._det_lanes)
+        scene = None
+        if wclip.want_scene_cuts:
+            from . import scene_detect
+
+            scene = scene_detect.SceneStream(wclip.H, wclip.W, device=dev)
+        sampled = {}
+        # a part whose frames lie in more than one window (every record is read and the windows are cut by frame count; the hole
+        # between two A/B sections may be many windows long) waits in `carry`: the frames it has so far, in order
+        carry = torch.empty((batch if wclip.carry_bytes else 0, wclip.H, wclip.W, 3), dtype=torch.uint8, device=dev)
+        state = {"frames": None, "slot": None}
+
+        def detect(detector, job):
+            part, carried = job
+            idx = torch.tensor([state["slot"][no - 1] for no in part[carried:]], dtype=torch.int64, device=dev)
+            frames = state["frames"][idx] if carried == 0 else torch.cat([carry[:carried], state["frames"][idx]])
+            if on_device:
+                return [[r] for r in detector.predict_batch_device(frames)]
+            return [detector.predict(f) for f in frames.cpu().numpy()]      # an injected detector with the reference's host signature
+
+        def run(jobs):
+            for (part, _), results in zip(jobs, batch_lanes.run_map(jobs, detectors, detect, dev)):
+                for no, res in zip(part, results):
+                    boxes = self._keep_inside(res)
+                    if len(boxes) > 0:
+                        sampled[no] = boxes
+
+        at, carried = 0, 0                                 # the next part, and how many of its frames are in `carry`
+        with contextlib.closing(wclip.stream_pass_a(units)) as windows:
+            for k, frames in windows:
+                read = units[k][:frames.shape[0]]
+                state["frames"], state["slot"] = frames, {f: i for i, f in enumerate(read)}
+                last, jobs = (read[-1] if read else -1), []
+                while at < len(parts) and parts[at][-1] - 1 <= last:
+                    jobs.append((parts[at], carried))
+                    at, carried = at + 1, 0
+                run(jobs)
+                if at < len(parts):                        # the part that goes on in a later window: what this one holds of it
+                    here = [state["slot"][no - 1] for no in parts[at][carried:] if no - 1 <= last]
+                    if here:
+                        carry[carried:carried + len(here)].copy_(frames[torch.tensor(here, dtype=torch.int64, device=dev)])
+                        carried += len(here)
+                if scene is not None:
+                    scene.feed(frames)
+                del frames
+            if carried:                                    # the file ended inside a part: the frames there are (as a resident clip's nos)
+                state["frames"], state["slot"] = carry[:0], {}
+                run([(parts[at][:carried], carried)])
+        state.clear()
+        del carry
+        torch.cuda.empty_cache()                           # pass B's buffers take the place of pass A's, not room next to them
+        if scene is not None:
+            wclip.scene_cuts = wclip.report["scene_cuts"] = scene.cuts()
         return self.fill_and_unify(sampled)
 
     def fill_and_unify(self, sampled):

@@ -543,6 +543,19 @@ class Y4mVideo:
             return None
         return {"path": os.path.abspath(self.path), "data_offset": self._data0, "prefix": b"FRAME\n", "frame_bytes": self._fsize, "count": total // rec}
 
+    def whole_records(self):
+        """how many frames read_planes_into will deliver: info()["len"] counts the FRAME lines, a last record cut short has one"""
+        layout = self.record_layout()
+        if layout is not None:
+            return int(layout["count"])
+        size, n = os.path.getsize(self.path), 0
+        with open(self.path, "rb") as f:
+            f.seek(self._data0)
+            while f.readline().startswith(b"FRAME") and f.tell() + self._fsize <= size:
+                f.seek(self._fsize, 1)
+                n += 1
+        return n
+
     def read_planes_into(self, out):
         """fill out[k] (uint8 [n][frame_bytes], e.g. pinned memory) with the next frames as stored; returns how many were read"""
         k = 0
