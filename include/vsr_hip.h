@@ -95,6 +95,16 @@ int vsr_sttn_auto_chunk_rows(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, i
 int vsr_sttn_auto_chunk_box(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev,
                             int n_areas, const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols,
                             const int32_t* sel, int nsel, void* stream);
+/* ... with look-back context (sttn-auto only; not in the reference): ctx_dev uint8 [n_ctx][H][W][3], frames of the same geometry that
+ * come BEFORE the L of frames_dev in the video.  The result written into frames_dev is what vsr_sttn_auto_chunk_box writes into the last
+ * L (selected) frames of the list ctx ++ frames -- the same windows and reference indices, bit for bit -- but ctx_dev is a pointer of
+ * its own, is only read, and nothing is decoded, averaged or resized back for it: a window none of whose neighbours is written is
+ * not run at all (Plan::nCtx).  n_ctx = 0 (ctx_dev ignored) is vsr_sttn_auto_chunk_box.  At most 127 context frames. */
+int vsr_sttn_auto_chunk_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev,
+                            int n_areas, const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols,
+                            const int32_t* sel, int nsel, const uint8_t* ctx_dev, int n_ctx, void* stream);
+/* FLOPs of that call's plan: a list of L frames (context included) whose first n_ctx are context, decoder box as vsr_sttn_flops_box */
+double vsr_sttn_flops_ctx(vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi);
 /* the column half of the same two questions (what VSR_DECODE_COLS=1 makes vsr_sttn_auto_chunk_box / vsr_sttn_det_batch_box do): the model columns
  * [*col_lo, *col_hi) decoded for a mask in frame columns [mask_col_lo, mask_col_hi) of a frame_w-wide frame (0, 0: all), and the
  * FLOPs of a plan restricted to a box of model rows and columns */
@@ -653,6 +663,8 @@ typedef struct VsrSoftmaxInfo {
 int vsr_plan_create(const vsr_sttn_t* h, int L, vsr_plan_t** out);
 int vsr_plan_create_rows(const vsr_sttn_t* h, int L, int row_lo, int row_hi, vsr_plan_t** out);   /* the decoder on model rows [row_lo, row_hi) only */
 int vsr_plan_create_box(const vsr_sttn_t* h, int L, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);   /* ... and columns */
+/* ... of L frames whose first n_ctx are read-only context (vsr_sttn_auto_chunk_ctx); works on a host-only handle like the others */
+int vsr_plan_create_ctx(const vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);
 int vsr_raft_plan_create(const vsr_raft_t* h, int t, int H, int W, int iters, vsr_plan_t** out);
 int vsr_rfc_plan_create(const vsr_rfc_t* h, int t, int H, int W, vsr_plan_t** out);
 int vsr_pp_imgprop_plan_create(int t, int H, int W, vsr_plan_t** out);

@@ -6,6 +6,7 @@ Mirrors backend/inpaint/sttn_auto_inpaint.py:
       inpaint(frames) -> comp frames                      :122-164
       get_ref_index(neighbor_ids, length)                 :107-120
   STTNAutoInpaint(device, model_path, video_path, mask_path=None, clip_gap=None)   :182-197
+      (+ context=None, scene_split=None: look-back context frames and scene-bounded chunks, not in the reference -- _run)
       __call__(input_mask=None, input_sub_remover=None, tbar=None)                 :199-336
 
 Arithmetic happens in libvsr_hip.so (there is no torch model and no CPU path here); this file
@@ -102,8 +103,9 @@ class _ResidentFrames:
 
 
 class STTNAutoInpaint:
-    def __init__(self, device, model_path, video_path, mask_path=None, clip_gap=None):
+    def __init__(self, device, model_path, video_path, mask_path=None, clip_gap=None, context=None, scene_split=None):
         self.sttn_inpaint = STTNInpaint(device, model_path)
+        self.context, self.scene_split = context, scene_split    # None: VSR_STTN_CONTEXT / VSR_SCENE_SPLIT (tools/chunk_parallel.lookback_options)
         self.video_path = video_path
         self.mask_path = mask_path
         if isinstance(video_path, (str, os.PathLike)):
@@ -128,11 +130,31 @@ class STTNAutoInpaint:
         (`dist`) the chunks are dealt round-robin and rank 0 owns the frame source and sink.  Chunk boundaries are the
         reference's (clip_gap), so every frame sees exactly the temporal context it sees in the reference.  Only the rows
         between the first and the last strip travel to the GPUs (nothing else can change, :314-315); the decoded frames stay
-        on the host and the returned rows are patched in before writing."""
+        on the host and the returned rows are patched in before writing.
+
+        Two options that are not the reference's, both off by default (then `ranges`, the engine calls and every byte are the
+        reference's).  scene_split: one scene-detection pass first (the ContentDetector pass of propainter mode), and the chunk grid
+        restarts at every cut (cp.scene_chunk_ranges): no chunk feeds frames of another scene to the attention.  context = N: a chunk
+        that continues a scene also sees the N SOURCE frames in front of it (never an inpainted result, never across a cut): the
+        strip rows of a chunk's last N frames are copied aside on the device before it is inpainted and handed to the next chunk's
+        engine call (SttnEngine.auto_chunk(context=...)), which reads them and writes the chunk alone.  One process only."""
         from ..tools import chunk_parallel as cp
 
+        n_context, scene_split = cp.lookback_options(self.context, self.scene_split, self.clip_gap)      # bad values: before any frame is read
+        if (n_context or scene_split) and dist is not None:
+            raise RuntimeError("sttn-auto context frames / scene-bounded chunks run in one process: a chunk looks back at its predecessor's "
+                               f"frames, which another rank holds (world size {dist.get_world_size()}); run without them or on one GPU")
         rank = dist.get_rank() if dist is not None else 0
         engine = self.sttn_inpaint.engine
+        cuts = []
+        if scene_split:
+            # a pass of its own over the source, before the chunk loop opens it: the call propainter_mode makes (backend/main.py), so
+            # the cuts are the ones pinned to the reference's SceneManager; its numbers are 1-based
+            from ..tools.subtitle_detect import SubtitleDetect
+
+            timed = getattr(input_sub_remover, "_timed", None) or (lambda _name, fn, *a: fn(*a))
+            cuts = [p - 1 for p in timed("scene cuts", SubtitleDetect.get_scene_div_frame_no, self.video_path, engine.device_index)]
+        self.scene_cuts = cuts
         reader = open_video(self.video_path)
         frame_info = reader.info()
         W_ori, H_ori = frame_info["W_ori"], frame_info["H_ori"]
@@ -143,7 +165,9 @@ class STTNAutoInpaint:
         mask = self.sttn_inpaint.read_mask(self.mask_path) if input_mask is None else threshold_mask(input_mask)
         inpaint_area = get_inpaint_area_by_mask(W_ori, H_ori, int(W_ori * 3 / 16), mask)
         # the reference clamps clip_gap by free VRAM / (W*H*12 B) (:228-238); 288 GB never binds
-        ranges = cp.chunk_ranges(frame_info["len"], self.clip_gap)
+        ranges = cp.scene_chunk_ranges(frame_info["len"], self.clip_gap, cuts)
+        scene_starts = {0} | set(cuts)
+        look = {"bufs": None, "turn": 0, "saved": None}
         y_lo = min((a[0] for a in inpaint_area), default=0)
         y_hi = max((a[1] for a in inpaint_area), default=0)
         local_areas = [(a[0] - y_lo, a[1] - y_lo, a[2], a[3]) for a in inpaint_area]
@@ -178,9 +202,21 @@ class STTNAutoInpaint:
         def process(i, rows):
             s, e = ranges[i]
             n = len(kept[i]) if i in kept else e - s     # the owner of the frame source knows how many frames were read
+            context = None
+            if n_context:
+                # look-back: the last source rows of the chunk before (what was read of it) unless this one starts a scene; this
+                # chunk's own last rows go into the spare buffer BEFORE it is inpainted (same stream, chunk order)
+                context = look["saved"] if s not in scene_starts else None
+                if look["bufs"] is None:
+                    look["bufs"] = [torch.empty((n_context,) + tuple(rows.shape[1:]), dtype=torch.uint8, device=rows.device) for _ in range(2)]
+                look["turn"] ^= 1
+                k = min(n_context, n)
+                look["saved"] = look["bufs"][look["turn"]][:k] if k else None
+                if k:
+                    look["saved"].copy_(rows[n - k:n])
             sel = [j - s for j in range(s, s + n) if is_frame_number_in_ab_sections(j, ab_sections)]
             if sel:
-                engine.auto_chunk(rows[:n], dmask, local_areas, sel=None if len(sel) == n else sel, mask_host=mask_rows_host)
+                engine.auto_chunk(rows[:n], dmask, local_areas, sel=None if len(sel) == n else sel, mask_host=mask_rows_host, context=context)
 
         def store(i, rows):
             for j, frame in enumerate(kept.pop(i)):
@@ -189,7 +225,8 @@ class STTNAutoInpaint:
                 writer.write(frame)
                 tick(original, frame)
 
-        local = self._rank_local_io(dist, rank, reader, writer, gui, inpaint_area, frame_info["len"])
+        # (the by-offset path deals whole chunks to workers with no order between them: with a look-back the funnel path is taken)
+        local = None if (n_context or scene_split) else self._rank_local_io(dist, rank, reader, writer, gui, inpaint_area, frame_info["len"])
         if local is not None:
             # every rank reads and writes its own chunks by offset (tools/rank_io.py): no rank-0 funnel, no collective on the data path
             try:

@@ -630,6 +630,10 @@ def main(argv=None):
         os.environ["VSR_Y4M_OUT"] = args.y4m_out
     if args.resident_windows:
         os.environ["VSR_IO_RESIDENT"] = "windows"
+    if args.scene_split:
+        os.environ["VSR_SCENE_SPLIT"] = "1"
+    if args.sttn_context is not None:
+        os.environ["VSR_STTN_CONTEXT"] = str(args.sttn_context)
     sr = SubtitleRemover(args.input)
     sr.sub_areas = [tuple(c) for c in args.subtitle_area_coords]
     if args.output is not None:

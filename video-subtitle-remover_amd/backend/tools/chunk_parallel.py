@@ -43,6 +43,45 @@ def chunk_ranges(total_frames, clip_gap):
     return [(i * clip_gap, min((i + 1) * clip_gap, total_frames)) for i in range(n)]
 
 
+def scene_chunk_ranges(total_frames, clip_gap, cuts):
+    """chunk_ranges with the grid restarted at every scene start (not in the reference, whose STTN modes chunk straight across
+    cuts): `cuts` = 0-based indices of the frames that start a new scene.  Scene [c_k, c_k+1) gives the pieces
+    [c_k + i * clip_gap, min(c_k + (i + 1) * clip_gap, c_k+1)): no piece holds a cut in its interior, none is longer than clip_gap.
+    Without cuts: exactly chunk_ranges."""
+    starts = [0] + sorted({int(c) for c in cuts if 0 < int(c) < total_frames})
+    out = []
+    for c, nxt in zip(starts, starts[1:] + [total_frames]):
+        out += [(c + s, c + e) for s, e in chunk_ranges(nxt - c, clip_gap)]
+    return out
+
+
+def context_span(piece_start, scene_start, n_context):
+    """(lo, hi): the source frames a piece starting at `piece_start` looks back at -- the n_context in front of it, never across the
+    start of its scene (nor frame 0, the first scene's start)"""
+    return max(piece_start - int(n_context), scene_start), piece_start
+
+
+def lookback_options(context, scene_split, clip_gap, env=None):
+    """(n_context, scene_split) of an sttn-auto run: the constructor's arguments, None = the environment (VSR_STTN_CONTEXT, an
+    integer; VSR_SCENE_SPLIT=1).  Off by default.  ValueError for a context that is no integer in [0, clip_gap]."""
+    import os
+
+    env = os.environ if env is None else env
+    if scene_split is None:
+        scene_split = env.get("VSR_SCENE_SPLIT", "0") == "1"
+    if context is None:
+        context = env.get("VSR_STTN_CONTEXT", "0") or "0"
+    try:
+        n = int(context)
+        if isinstance(context, float) and n != context:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"sttn-auto context: {context!r} is not an integer") from None
+    if n < 0 or n > int(clip_gap):
+        raise ValueError(f"sttn-auto context: {n} frames asked for, 0 <= N <= clip_gap = {int(clip_gap)} are possible")
+    return n, bool(scene_split)
+
+
 def owner_of(chunk_index, world_size):
     return chunk_index % world_size
 

@@ -171,12 +171,15 @@ static int gg_wide_queues()
 
 
 // decLo / decHi: the rows of the model-resolution output the caller will read (Plan::decLo; 0, 0 = all)
-static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0)
+// nCtx: the first nCtx of the L frames are read-only context (Plan::nCtx)
+static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0, int nCtx = 0)
 {
     // the key packs the four decoder bounds into 10 bits each
     if (h->model.g.modelH >= 1024 || h->model.g.modelW >= 1024 || decLo < 0 || decHi >= 1024 || decXLo < 0 || decXHi >= 1024)
         return fail(VSR_ERR_ARG, "plan key: model resolution / decoder bounds beyond 1023");
-    const int64_t key = ((((((int64_t)L * 4 + precision) * 8 + h->lanes) * 1024 + decLo) * 1024 + decHi) * 1024 + decXLo) * 1024 + decXHi;
+    // (L sits above bit 45; the context count takes the seven bits from 56 up, 0 = the key of old)
+    if (nCtx < 0 || nCtx >= 128 || (nCtx > 0 && L >= 2048)) return fail(VSR_ERR_ARG, "plan key: at most 127 context frames, in a list of at most 2047");
+    const int64_t key = (((((((int64_t)L * 4 + precision) * 8 + h->lanes) * 1024 + decLo) * 1024 + decHi) * 1024 + decXLo) * 1024 + decXHi) + ((int64_t)nCtx << 56);
     const bool fmt = precision >= 2;       // split-format tensors: everything a GEMM reads (see gather_gemm_v5.h)
     auto plainF32 = [](int buf) { buf = baseBuf(buf); return buf == BUF_S || buf == BUF_PVPART || buf == BUF_D4 || buf == BUF_COMP; };
     if (fmt && !h->weightsSplit) {
@@ -191,7 +194,7 @@ static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int 
     std::unique_ptr<PlanDev> pd(new PlanDev);
     pd->lastUse = ++h->useClock;
     try {
-        pd->plan.reset(new Plan(h->model, L, precision, h->lanes, decLo, decHi, decXLo, decXHi));
+        pd->plan.reset(new Plan(h->model, L, precision, h->lanes, decLo, decHi, decXLo, decXHi, nCtx));
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());
     }
@@ -853,7 +856,7 @@ static void model_cols_of_mask(bool det, int mw, int W, int c0, int c1, int* lo,
 
 static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
                          const int32_t* areas, const int32_t* sel, int nsel, hipStream_t stream, const int32_t* maskRows = nullptr,
-                         const int32_t* maskCols = nullptr)
+                         const int32_t* maskCols = nullptr, const uint8_t* ctx_dev = nullptr, int nCtx = 0)
 {
     if (!frames_dev || !mask_dev || L <= 0 || H <= 0 || W <= 0 || n_areas < 0 || (n_areas > 0 && !areas))
         return fail(VSR_ERR_ARG, "bad argument");
@@ -861,6 +864,9 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
     const Geometry& g = h->model.g;
     const int mw = g.modelW, mh = g.modelH;
     const int Ls = (sel && nsel > 0) ? nsel : L;
+    // look-back context (vsr_sttn_auto_chunk_ctx): the plan's list is the nCtx context frames followed by the Ls selected ones; the
+    // context strips are resized in front of them, the blend reads the comp frames behind them and writes frames_dev alone
+    const int Lp = nCtx + Ls;
     const int32_t* dSel = nullptr;
     if (sel && nsel > 0) {
         for (int i = 0; i < nsel; ++i)
@@ -920,8 +926,8 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
         }
     }
     PlanDev* pd = nullptr;
-    RCCHK(build_plan_dev(h, Ls, h->precision, &pd, decLo[0], decHi[0], decXLo[0], decXHi[0]));
-    const int64_t compElems = (int64_t)Ls * mh * mw * 3;
+    RCCHK(build_plan_dev(h, Lp, h->precision, &pd, decLo[0], decHi[0], decXLo[0], decXHi[0], nCtx));
+    const int64_t compElems = (int64_t)Lp * mh * mw * 3;
     if (n_areas > 1 && h->compAreasCap < compElems * n_areas) {
         if (h->compAreas) HIPCHK(hipFree(h->compAreas));
         HIPCHK(hipMalloc((void**)&h->compAreas, (size_t)(compElems * n_areas) * sizeof(float)));
@@ -938,14 +944,17 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
         if (ymin < 0 || ymax > H || sh <= 0) return fail(VSR_ERR_ARG, "inpaint area outside the frame");
         StripTables* st = nullptr;
         RCCHK(get_strip_tables(h, W, sh, &st));
-        if (vsr_launch_resize_u8(frames_dev + (int64_t)ymin * W * 3, frameStride, W * 3, W, sh, (uint8_t*)h->bufs[BUF_IN_U8], mw,
+        if (nCtx > 0 && vsr_launch_resize_u8(ctx_dev + (int64_t)ymin * W * 3, frameStride, W * 3, W, sh, (uint8_t*)h->bufs[BUF_IN_U8], mw,
+                                             mh, nCtx, 3, nullptr, st->dxofs, st->dialpha, st->dyofs, st->dibeta, stream) != 0)
+            return fail(VSR_ERR_HIP, "context resize launch failed");
+        if (vsr_launch_resize_u8(frames_dev + (int64_t)ymin * W * 3, frameStride, W * 3, W, sh, (uint8_t*)h->bufs[BUF_IN_U8] + (int64_t)nCtx * mh * mw * 3, mw,
                                  mh, Ls, 3, dSel, st->dxofs, st->dialpha, st->dyofs, st->dibeta, stream) != 0)
             return fail(VSR_ERR_HIP, "resize launch failed");
         if (det) // cv2.resize(mask_crop, (432, 240)) -- the same strip mask for every frame (frame stride 0)
             if (vsr_launch_resize_u8(mask_dev + (int64_t)ymin * W, 0, W, W, sh, (uint8_t*)h->bufs[BUF_MASK_U8], mw, mh, Ls, 1,
                                      nullptr, st->dxofs, st->dialpha, st->dyofs, st->dibeta, stream) != 0)
                 return fail(VSR_ERR_HIP, "mask resize launch failed");
-        if (k > 0 || attempt > 0) RCCHK(build_plan_dev(h, Ls, attempt ? 0 : h->precision, &pd, decLo[k], decHi[k], decXLo[k], decXHi[k]));
+        if (k > 0 || attempt > 0) RCCHK(build_plan_dev(h, Lp, attempt ? 0 : h->precision, &pd, decLo[k], decHi[k], decXLo[k], decXHi[k], nCtx));
         RCCHK(run_plan(h, pd, stream));
         if (n_areas > 1)
             HIPCHK(hipMemcpyAsync(h->compAreas + compElems * k, h->bufs[BUF_COMP], (size_t)compElems * sizeof(float),
@@ -960,8 +969,8 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
         const int sh = ymax - ymin;
         StripTables* st = nullptr;
         RCCHK(get_strip_tables(h, W, sh, &st));
-        const float* comp = n_areas > 1 ? h->compAreas + compElems * k : (const float*)h->bufs[BUF_COMP];
-        if (vsr_launch_upscale_blend(comp, mw, mh, pd->dIsFloat, frames_dev + (int64_t)ymin * W * 3, frameStride, W * 3, dSel,
+        const float* comp = (n_areas > 1 ? h->compAreas + compElems * k : (const float*)h->bufs[BUF_COMP]) + (int64_t)nCtx * mh * mw * 3;
+        if (vsr_launch_upscale_blend(comp, mw, mh, pd->dIsFloat + nCtx, frames_dev + (int64_t)ymin * W * 3, frameStride, W * 3, dSel,
                                      det ? nullptr : mask_dev + (int64_t)ymin * W, W, W, sh, Ls, st->uxofs, st->uialpha,
                                      st->ufalpha, st->uyofs, st->uibeta, st->ufbeta, stream) != 0)
             return fail(VSR_ERR_HIP, "blend launch failed");
@@ -992,6 +1001,29 @@ int vsr_sttn_auto_chunk_box(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, in
     RCCHK(need_gpu(h));
     if (h->model.g.variant != VSR_VARIANT_STTN_AUTO) return fail(VSR_ERR_STATE, "not an sttn-auto model");
     return strips_common(h, false, frames_dev, L, H, W, mask_dev, n_areas, areas, sel, nsel, (hipStream_t)stream_, mask_rows, mask_cols);
+}
+
+int vsr_sttn_auto_chunk_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
+                            const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const int32_t* sel, int nsel,
+                            const uint8_t* ctx_dev, int n_ctx, void* stream_)
+{
+    RCCHK(need_gpu(h));
+    if (h->model.g.variant != VSR_VARIANT_STTN_AUTO) return fail(VSR_ERR_STATE, "not an sttn-auto model");
+    if (n_ctx < 0 || (n_ctx > 0 && !ctx_dev)) return fail(VSR_ERR_ARG, "bad context");
+    return strips_common(h, false, frames_dev, L, H, W, mask_dev, n_areas, areas, sel, nsel, (hipStream_t)stream_, mask_rows, mask_cols,
+                         n_ctx > 0 ? ctx_dev : nullptr, n_ctx);
+}
+
+double vsr_sttn_flops_ctx(vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi)
+{
+    if (!h || !h->model.packed_ready() || L <= 0) { fail(VSR_ERR_ARG, "bad argument"); return -1.0; }
+    try {
+        Plan p(h->model, L, 0, 1, row_lo, row_hi, col_lo, col_hi, n_ctx);
+        return p.flops;
+    } catch (const std::exception& e) {
+        fail(VSR_ERR_ARG, e.what());
+        return -1.0;
+    }
 }
 
 double vsr_sttn_flops_rows(vsr_sttn_t* h, int L, int row_lo, int row_hi)
@@ -1377,6 +1409,19 @@ int vsr_plan_create_box(const vsr_sttn_t* h, int L, int row_lo, int row_hi, int 
     try {
         std::unique_ptr<vsr_plan> p(new vsr_plan);
         p->plan.reset(new Plan(h->model, L, 0, h->lanes, row_lo, row_hi, col_lo, col_hi));
+        *out = p.release();
+    } catch (const std::exception& e) {
+        return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());
+    }
+    return 0;
+}
+int vsr_plan_create_ctx(const vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out)
+{
+    if (!h || !out || L <= 0) return fail(VSR_ERR_ARG, "bad argument");
+    if (!h->model.packed_ready()) return fail(VSR_ERR_STATE, "model not finalized");
+    try {
+        std::unique_ptr<vsr_plan> p(new vsr_plan);
+        p->plan.reset(new Plan(h->model, L, 0, h->lanes, row_lo, row_hi, col_lo, col_hi, n_ctx));
         *out = p.release();
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());

@@ -547,8 +547,12 @@ void Plan::addConv(const char* tag, const Act& in, const std::vector<int>& inIds
 // the rows of its neighbour frames (Plan::buildWindow)
 // [attLo, attHi): the feature rows of the attention output that anything reads (the last block of a window that feeds a ranged
 // decoder): the query tokens are the patches that touch those rows
-void Plan::addAttention(int Tq, int T, const BlockW&, int attLo, int attHi, int attXLo, int attXHi, int qkvBuf, const std::vector<int>* fids)
+void Plan::addAttention(int Tq, int T, const BlockW&, int attLo, int attHi, int attXLo, int attXHi, int qkvBuf, const std::vector<int>* fids, int qFirst)
 {
+    // the q/k/v frames of the query tokens: the first Tq of the window, or (a window whose first neighbours are context) Tq from qFirst on
+    std::vector<int> qf;
+    for (int t = 0; t < Tq; ++t) qf.push_back(fids ? (*fids)[qFirst + t] : qFirst + t);
+    const std::vector<int>* qfids = qFirst > 0 ? &qf : fids;
     if (qkvBuf < 0) qkvBuf = lb(BUF_QKV);
     if (attHi < 0) attHi = g.featH;
     if (attXHi < 0) attXHi = g.featW;
@@ -587,7 +591,7 @@ void Plan::addAttention(int Tq, int T, const BlockW&, int attLo, int attHi, int 
         a.splitK = splitK; a.chunksPerSplit = cps; a.splitStride = plane;
         a.alpha = 1.f; a.act = VSR_ACT_NONE;
         a.bufA = qkvBuf; a.offA = 0;
-        a.tRowA = tRowsTokens(Tq, s, dk * s, Mtok, qBM, oy0, oy1, ox0, ox1, fids);
+        a.tRowA = tRowsTokens(Tq, s, dk * s, Mtok, qBM, oy0, oy1, ox0, ox1, qfids);
         a.tColA = tColsPatch(s, nchunks);
         a.bufB = qkvBuf; a.offB = 0;
         a.tRowB = tRowsTokens(T, s, C + dk * s, Ntok, qBN, 0, -1, 0, -1, fids);
@@ -693,6 +697,11 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
     std::vector<int> ids = neighbors;
     ids.insert(ids.end(), refs.begin(), refs.end());
     const int T = (int)ids.size(), nn = (int)neighbors.size();
+    // look-back context (Plan::nCtx): the neighbours are ascending, so the read-only ones are the first q0 of them; the last block's
+    // query rows and the decoder are built for the nw written ones, which the window's buffers then hold from frame 0 on
+    int q0 = 0;
+    while (q0 < nn && neighbors[q0] < nCtx) ++q0;
+    const int nw = nn - q0;
     const Act feats{BUF_FEATS, L, fh, fw, C, 2};
     const Act x0{lb(BUF_X0), T, fh, fw, C, 2}, x1{lb(BUF_X1), T, fh, fw, C, 2};
     const Act att{lb(BUF_ATT), T, fh, fw, C, 1}, f1{lb(BUF_F1), T, fh, fw, C, 1};
@@ -766,8 +775,9 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         // [lastLo, lastHi) of the last block's output (the chain is walked backwards at the top of this function), its second 3x3
         // conv needs one more row of the first conv's output on each side, the first (dilation 2) two more of the out-conv's, the
         // out-conv one more of the attention output, and the attention output rows belong to the patches that touch them.
-        const bool last = tu_.trimLastBlock && b == g.blocks - 1;
-        const int Tq = last ? nn : T;
+        // (a window with context neighbours is trimmed whatever the switch says: the decoder addresses the written frames from 0 on)
+        const bool last = (tu_.trimLastBlock || q0 > 0) && b == g.blocks - 1;
+        const int Tq = last ? nw : T, qFirst = last ? q0 : 0;
         const int r2lo = last ? lastLo : 0, r2hi = last ? lastHi : fh;                       // ffn.2 output = the block's output
         auto wide = [&](int lo, int hi, int by, int& olo, int& ohi) { olo = lo - by > 0 ? lo - by : 0; ohi = hi + by < fh ? hi + by : fh; };
         int r1lo, r1hi, r0lo, r0hi, ralo, rahi;
@@ -776,10 +786,10 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         wide(r2lo, r2hi, 4, ralo, rahi);                                                       // attention output
         const Rng c2 = last ? cX1 : Rng{0, fw}, c1 = widen(c2, 1, fw), c0 = widen(c2, 3, fw), ca = widen(c2, 4, fw);   // the same along x
         const std::vector<int> idQ = iota(Tq);
-        const std::vector<int> curIdsQ(curIds.begin(), curIds.begin() + Tq);
+        const std::vector<int> curIdsQ(curIds.begin() + qFirst, curIds.begin() + qFirst + Tq);
         const double before = flops;
-        if (shared0) addAttention(Tq, T, bw, ralo, rahi, ca.lo, ca.hi, BUF_QKV0, &ids);
-        else addAttention(Tq, T, bw, ralo, rahi, ca.lo, ca.hi);
+        if (shared0) addAttention(Tq, T, bw, ralo, rahi, ca.lo, ca.hi, BUF_QKV0, &ids, qFirst);
+        else addAttention(Tq, T, bw, ralo, rahi, ca.lo, ca.hi, -1, nullptr, qFirst);
         // x = x + LeakyReLU(conv3x3(att))            (auto_sttn.py:162-164,237)
         addConv("attn.out", att, idQ, x0, Tq, 3, 1, 1, bw.out, VSR_ACT_LRELU02, &cur, &curIdsQ, r0lo, r0hi, c0.lo, c0.hi);
         // x = x + LeakyReLU(conv3x3(LeakyReLU(conv3x3 dil2(x))))   (auto_sttn.py:214-218,238)
@@ -791,15 +801,15 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         curIds = idT;
     }
 
-    // decoder on the neighbour frames only (sttn_auto_inpaint.py:150; auto_sttn.py:87-95,118-127)
-    const Act up1{lb(BUF_UP1), nn, 2 * fh, 2 * fw, C, 1}, d1{lb(BUF_D1), nn, 2 * fh, 2 * fw, 128, 1};
-    const Act d2{lb(BUF_D2), nn, 2 * fh, 2 * fw, 64, 0}, up2{lb(BUF_UP2), nn, mh, mw, 64, 1}, d3{lb(BUF_D3), nn, mh, mw, 64, 1};
-    const std::vector<int> idN = iota(nn);
+    // decoder on the neighbour frames only (sttn_auto_inpaint.py:150; auto_sttn.py:87-95,118-127) -- the written ones (nw = nn without the context frames)
+    const Act up1{lb(BUF_UP1), nw, 2 * fh, 2 * fw, C, 1}, d1{lb(BUF_D1), nw, 2 * fh, 2 * fw, 128, 1};
+    const Act d2{lb(BUF_D2), nw, 2 * fh, 2 * fw, 64, 0}, up2{lb(BUF_UP2), nw, mh, mw, 64, 1}, d3{lb(BUF_D3), nw, mh, mw, 64, 1};
+    const std::vector<int> idN = iota(nw);
     {
         Op op;
         op.kind = OP_UPSAMPLE2X; op.tag = "dec.up1";
         op.bufSrc = x1.buf; op.H = fh; op.W = fw; op.C = C; op.haloS = x1.halo; op.bufDst = up1.buf; op.haloD = up1.halo;
-        op.n = nn;
+        op.n = nw;
         op.ipar[1] = rUp1.lo; op.ipar[2] = rUp1.hi;       // output rows
         need(up1.buf, up1.elems());
         ops.push_back(std::move(op));
@@ -809,20 +819,20 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         const double part = (double)(r.hi - r.lo) * (c.hi - c.lo);
         trimmedFlops_ += ops.back().flops * ((double)H * W - part) / part;
     };
-    addConv("dec.1", up1, idN, d1, nn, 3, 1, 1, m_.dec[0], VSR_ACT_LRELU02, nullptr, nullptr, rD1.lo, rD1.hi, cD1.lo, cD1.hi);
+    addConv("dec.1", up1, idN, d1, nw, 3, 1, 1, m_.dec[0], VSR_ACT_LRELU02, nullptr, nullptr, rD1.lo, rD1.hi, cD1.lo, cD1.hi);
     skipped(rD1, 2 * fh, cD1, 2 * fw);
-    addConv("dec.2", d1, idN, d2, nn, 3, 1, 1, m_.dec[1], VSR_ACT_LRELU02, nullptr, nullptr, rD2.lo, rD2.hi, cD2.lo, cD2.hi);
+    addConv("dec.2", d1, idN, d2, nw, 3, 1, 1, m_.dec[1], VSR_ACT_LRELU02, nullptr, nullptr, rD2.lo, rD2.hi, cD2.lo, cD2.hi);
     skipped(rD2, 2 * fh, cD2, 2 * fw);
     {
         Op op;
         op.kind = OP_UPSAMPLE2X; op.tag = "dec.up2";
         op.bufSrc = d2.buf; op.H = 2 * fh; op.W = 2 * fw; op.C = 64; op.haloS = d2.halo; op.bufDst = up2.buf;
-        op.haloD = up2.halo; op.n = nn;
+        op.haloD = up2.halo; op.n = nw;
         op.ipar[1] = rUp2.lo; op.ipar[2] = rUp2.hi;
         need(up2.buf, up2.elems());
         ops.push_back(std::move(op));
     }
-    addConv("dec.3", up2, idN, d3, nn, 3, 1, 1, m_.dec[2], VSR_ACT_LRELU02, nullptr, nullptr, rD3.lo, rD3.hi, cD3.lo, cD3.hi);
+    addConv("dec.3", up2, idN, d3, nw, 3, 1, 1, m_.dec[2], VSR_ACT_LRELU02, nullptr, nullptr, rD3.lo, rD3.hi, cD3.lo, cD3.hi);
     skipped(rD3, mh, cD3, mw);
     if (tu_.outConvBlocked && mh % Model::kOutBlkH == 0 && mw % Model::kOutBlkW == 0) {
         // 64 -> 3 conv over 2x4 output blocks (Model::pack_conv_blocked): row = block, columns (dy, dx, c) in a [blocks][32] buffer
@@ -834,21 +844,21 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         GemmItem it{};
         const int by0 = rOut.lo / bh, by1 = rOut.hi / bh;      // (decLo / decHi, decXLo / decXHi are whole blocks: Plan::Plan)
         const int bx0 = cOut.lo / bw, bx1 = cOut.hi / bw;
-        it.M = nn * (by1 - by0) * (bx1 - bx0); it.N = w.cout; it.K = w.K;
+        it.M = nw * (by1 - by0) * (bx1 - bx0); it.N = w.cout; it.K = w.K;
         it.tilesM = cdiv(it.M, BM); it.tilesN = 1;
         it.splitK = 1; it.chunksPerSplit = it.K / VSR_GG_KC; it.alpha = 1.f; it.act = VSR_ACT_NONE;
         it.bufA = d3.buf; it.offA = 0;
         std::vector<int32_t> crows;          // where a block's 32 columns go: the [frame][block row][block col] slot of the FULL image
         {   // rows: the block's top-left pixel; columns: the (bh+2) x (bw+2) window around the block, K order as packed
             std::vector<int32_t> rows;
-            for (int f = 0; f < nn; ++f)
+            for (int f = 0; f < nw; ++f)
                 for (int by = by0; by < by1; ++by)
                     for (int bx = bx0; bx < bx1; ++bx) {
                         rows.push_back((int32_t)d3.pix(f, by * bh, bx * bw));
                         crows.push_back((int32_t)((((int64_t)f * (mh / bh) + by) * (mw / bw) + bx) * 32));
                     }
             while ((int)rows.size() % BM) { rows.push_back(rows[0]); crows.push_back(crows[0]); }
-            it.tRowA = table("RBLK:" + std::to_string(nn) + ":" + std::to_string(mh) + "x" + std::to_string(mw) + ":" + std::to_string(by0) + "-" + std::to_string(by1) + ":" + std::to_string(bx0) + "-" + std::to_string(bx1), std::move(rows));
+            it.tRowA = table("RBLK:" + std::to_string(nw) + ":" + std::to_string(mh) + "x" + std::to_string(mw) + ":" + std::to_string(by0) + "-" + std::to_string(by1) + ":" + std::to_string(bx0) + "-" + std::to_string(bx1), std::move(rows));
             std::vector<int32_t> cols;
             auto off = [&](int wy, int wx, int c) { return (int32_t)(((int64_t)(wy - 1) * d3.Wp() + (wx - 1)) * d3.C + c); };
             if (tu_.convChannelMajor) {
@@ -866,14 +876,14 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         it.tRowB = tRowsLinear(it.N, it.K, BN);
         it.tColB = tColsLinear(it.K / VSR_GG_KC, it.K / VSR_GG_KC);
         it.bufC = lb(BUF_D4); it.offC = 0;
-        it.tRowC = table("CBLKROW:" + std::to_string(nn) + ":" + std::to_string(mh) + "x" + std::to_string(mw) + ":" + std::to_string(by0) + "-" + std::to_string(by1) + ":" + std::to_string(bx0) + "-" + std::to_string(bx1), std::move(crows));
+        it.tRowC = table("CBLKROW:" + std::to_string(nw) + ":" + std::to_string(mh) + "x" + std::to_string(mw) + ":" + std::to_string(by0) + "-" + std::to_string(by1) + ":" + std::to_string(bx0) + "-" + std::to_string(bx1), std::move(crows));
         it.tColC = tColsLinear(1, 1);
         it.offBias = w.b;
         it.bufR = -1; it.tRowR = -1;
-        op.flops = 2.0 * (double)nn * (rOut.hi - rOut.lo) * (cOut.hi - cOut.lo) * 3.0 * (9.0 * d3.C);     // the algorithmic work of the 3x3 conv, not the padded window's
+        op.flops = 2.0 * (double)nw * (rOut.hi - rOut.lo) * (cOut.hi - cOut.lo) * 3.0 * (9.0 * d3.C);     // the algorithmic work of the 3x3 conv, not the padded window's
         flops += op.flops;
         op.gemm.push_back(it);
-        need(lb(BUF_D4), (int64_t)cdiv(nn * (mh / bh) * (mw / bw), BM) * BM * 32);
+        need(lb(BUF_D4), (int64_t)cdiv(nw * (mh / bh) * (mw / bw), BM) * BM * 32);
         ops.push_back(std::move(op));
         skipped(rOut, mh, cOut, mw);
     } else
@@ -884,7 +894,7 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         const int BM = 256, BN = 32;
         GemmItem it{};
         if (ranged) throw std::runtime_error("a decoder row range needs the blocked output conv (VSR_OUT_CONV_BLOCKED=1)");
-        it.M = nn * mh * mw; it.N = w.cout; it.K = w.K;
+        it.M = nw * mh * mw; it.N = w.cout; it.K = w.K;
         it.tilesM = cdiv(it.M, BM); it.tilesN = 1;
         it.splitK = 1; it.chunksPerSplit = it.K / VSR_GG_KC; it.alpha = 1.f; it.act = VSR_ACT_NONE;
         it.bufA = d3.buf; it.offA = 0;
@@ -907,16 +917,16 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
     {
         Op op;
         op.kind = OP_DECODE_OUT; op.tag = "dec.out";
-        op.bufSrc = lb(BUF_D4); op.bufDst = BUF_COMP; op.ldy = 32; op.pix = mh * mw; op.n = nn;
+        op.bufSrc = lb(BUF_D4); op.bufDst = BUF_COMP; op.ldy = 32; op.pix = mh * mw; op.n = nw;
         op.ipar[1] = rOut.lo; op.ipar[2] = rOut.hi;       // rows of the mw-wide image that are decoded and averaged
         if (g.variant == 1) { op.ipar[1] = 0; op.ipar[2] = mh; }   // sttn-det: the rows without mask take the input frame here (below), every row is written
         if (tu_.outConvBlocked && mh % Model::kOutBlkH == 0 && mw % Model::kOutBlkW == 0) op.W = mw;   // src rows are 2x4 blocks of a mw-wide image
         op.bufMask = g.variant == 1 ? BUF_MASK_U8 : -1;   // sttn-det: model-resolution blend with the input frames
         std::vector<int32_t> fi, fs;
-        for (int i = 0; i < nn; ++i) {
-            fi.push_back(neighbors[i]);
-            fs.push_back(visits[neighbors[i]] == 0 ? 1 : 0);
-            visits[neighbors[i]]++;
+        for (int i = 0; i < nw; ++i) {
+            fi.push_back(neighbors[q0 + i]);
+            fs.push_back(visits[neighbors[q0 + i]] == 0 ? 1 : 0);
+            visits[neighbors[q0 + i]]++;
         }
         std::string k1 = "FI:", k2 = "FS:";
         for (int v : fi) k1 += std::to_string(v) + ",";
@@ -950,12 +960,14 @@ void Plan::decoder_bounds(const Geometry& g, int precision, int decLo_, int decH
     *lo = decLo; *hi = decHi; *xlo = decXLo; *xhi = decXHi;
 }
 
-Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, int decHi_, int decXLo_, int decXHi_)
-    : L(L_), precision(precision_), lanes(lanes_ < 1 ? 1 : (lanes_ > kMaxLanes ? kMaxLanes : lanes_)), g(model.g), m_(model), tu_(Tuning::get(precision_))
+Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, int decHi_, int decXLo_, int decXHi_, int nCtx_)
+    : L(L_), nCtx(nCtx_), precision(precision_), lanes(lanes_ < 1 ? 1 : (lanes_ > kMaxLanes ? kMaxLanes : lanes_)), g(model.g), m_(model), tu_(Tuning::get(precision_))
 {
     decoder_bounds(g, precision_, decLo_, decHi_, decXLo_, decXHi_, &decLo, &decHi, &decXLo, &decXHi);
     if (!model.packed_ready()) throw std::runtime_error("model weights are not packed");
     if (L <= 0) throw std::runtime_error("empty frame list");
+    if (nCtx < 0 || nCtx >= L) throw std::runtime_error("context frames: 0 <= n_ctx < frames of the list");
+    if (nCtx > 0 && g.variant != 0) throw std::runtime_error("context frames are an sttn-auto option");
     bufElems.assign(BUF_COUNT, 0);
     bufElems[BUF_WEIGHTS] = (int64_t)model.packed.size();
     const int mh = g.modelH, mw = g.modelW, fh = g.featH, fw = g.featW, C = g.channels;
@@ -1051,6 +1063,7 @@ Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, i
             for (int n : neighbors) inN |= (n == i);
             if (!inN) refs.push_back(i);
         }
+        if (neighbors.back() < nCtx) continue;     // no written neighbour: nothing of this window is read (Plan::nCtx)
         // windows are independent until OP_DECODE_OUT averages their frames into BUF_COMP (in window order): window w works in
         // lane w % lanes' buffers and is issued on that lane's stream
         lane_ = nwindows % lanes;
@@ -1062,6 +1075,8 @@ Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, i
     lane_ = 0;
     compCount = visits;
     refFlops = flops + trimmedFlops_;
+    // (the reference runs the whole list: what it spends is the plain plan's count, dropped windows and context decodes included)
+    if (nCtx > 0) refFlops = Plan(model, L_, precision_, 1, decLo_, decHi_, decXLo_, decXHi_).refFlops;
 }
 
 // ------------------------------------------------------------------------------------

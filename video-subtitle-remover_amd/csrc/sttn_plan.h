@@ -199,13 +199,18 @@ public:
     // only where the mask is set: vsr_sttn_auto_chunk) -- the decoder computes those rows and what they depend on, nothing else
     // (buildWindow); decHi <= decLo = the whole image
     // decXLo / decXHi: the same for columns (the GEMMs take rectangles; the two elementwise kernels of the decoder keep whole rows)
-    Plan(const Model& model, int L, int precision = 0, int lanes = 1, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0);
+    // nCtx: the first nCtx frames of the list are look-back CONTEXT (sttn-auto, vsr_sttn_auto_chunk_ctx): read by every window that
+    // holds them -- as neighbours and as reference frames, at the positions a plain plan of L frames gives them -- and never written:
+    // the last block's query rows, the decoder and the running average in BUF_COMP are built for the other ("written") neighbours of a
+    // window only, and a window without one is not built at all.  The written frames come out with the bits of the plain plan of L.
+    Plan(const Model& model, int L, int precision = 0, int lanes = 1, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0, int nCtx = 0);
     // the bounds a plan with these arguments decodes: clipped to the image and widened to whole blocks of the output conv (all 0 = the
     // whole image: no promise, or the per-pixel form of the output conv).  Needs no plan: vsr_sttn_decode_rows asks once per area.
     static void decoder_bounds(const Geometry& g, int precision, int decLo, int decHi, int decXLo, int decXHi, int* lo, int* hi, int* xlo, int* xhi);
     int decLo = 0, decHi = 0;            // as given, clipped to the image and widened to whole 2-row blocks of the output conv
     int decXLo = 0, decXHi = 0;          // ... to whole 4-column blocks
     int L;
+    int nCtx = 0;                        // frames [0, nCtx) are read-only context; compCount of those stays 0
     int precision;
     int lanes;                           // 1 .. kMaxLanes: window w runs on lane w % lanes
     int firstWindowOp = -1;              // index of the first op that is not the encoder's: lane 1 may start once everything before it is done
@@ -232,8 +237,9 @@ private:
                  const std::vector<int>* resIds, int ylo = 0, int yhi = -1,      // [ylo, yhi): output rows computed (stride 1; default all)
                  int xlo = 0, int xhi = -1);                                       // [xlo, xhi): output columns computed (default all)
     // [attLo, attHi) x [attXLo, attXHi): feature rows / columns of the output that are read
+    // qFirst: the query frames are frames [qFirst, qFirst + Tq) of the T (their rows of the attention output are stored from frame 0 on)
     void addAttention(int Tq, int T, const BlockW& bw, int attLo = 0, int attHi = -1, int attXLo = 0, int attXHi = -1, int qkvBuf = -1,
-                      const std::vector<int>* fids = nullptr);
+                      const std::vector<int>* fids = nullptr, int qFirst = 0);
     void buildWindow(const std::vector<int>& neighbors, const std::vector<int>& refs,
                      std::vector<int32_t>& visits);
 };
