@@ -95,7 +95,7 @@ int vsr_sttn_auto_chunk_rows(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, i
 int vsr_sttn_auto_chunk_box(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev,
                             int n_areas, const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols,
                             const int32_t* sel, int nsel, void* stream);
-/* ... with look-back context (sttn-auto only; not in the reference): ctx_dev uint8 [n_ctx][H][W][3], frames of the same geometry that
+/* ... with look-back context (not in the reference; sttn-det: vsr_sttn_det_batch_ctx): ctx_dev uint8 [n_ctx][H][W][3], frames of the same geometry that
  * come BEFORE the L of frames_dev in the video.  The result written into frames_dev is what vsr_sttn_auto_chunk_box writes into the last
  * L (selected) frames of the list ctx ++ frames -- the same windows and reference indices, bit for bit -- but ctx_dev is a pointer of
  * its own, is only read, and nothing is decoded, averaged or resized back for it: a window none of whose neighbours is written is
@@ -135,6 +135,16 @@ int vsr_sttn_det_batch(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, 
  * frame -- the decoder runs on the model rows the mask rows are resized to; same frames */
 int vsr_sttn_det_batch_rows(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
                             const int32_t* areas, const int32_t* mask_rows, void* stream);
+/* vsr_sttn_det_batch_box with look-back context (not in the reference; extends STTNDetInpaint.__call__, :38-99, to a list whose head
+ * is read-only): ctx_dev uint8 [n_ctx][H][W][3], frames of the same geometry that come BEFORE the L of frames_dev in the video.  The
+ * result written into frames_dev is what vsr_sttn_det_batch_box writes into the last L frames of the list ctx ++ frames, bit for bit:
+ * the context strips get the same mask strip (:66-82), the same pre-masking of the encoder input (:143), the same windows and
+ * reference indices (:146-158), but ctx_dev is only read and nothing is decoded, blended, averaged or resized back for it (Plan::nCtx).
+ * mask_rows and mask_cols may each be null (no promise).  n_ctx = 0 (ctx_dev ignored) is vsr_sttn_det_batch_box.  At most 127 context
+ * frames.  vsr_sttn_flops_ctx and vsr_plan_create_ctx on a det handle give this call's plan. */
+int vsr_sttn_det_batch_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
+                           const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const uint8_t* ctx_dev, int n_ctx,
+                           void* stream);
 
 /* Arithmetic of the contractions.  0 (default): exact fp32 -- v_mfma_f32_32x32x2_f32, bitwise an fmaf chain.
  * 1: split-half -- fp32 data and fp32 accumulation, each fp32 operand fed to the f16 matrix cores as
@@ -663,7 +673,7 @@ typedef struct VsrSoftmaxInfo {
 int vsr_plan_create(const vsr_sttn_t* h, int L, vsr_plan_t** out);
 int vsr_plan_create_rows(const vsr_sttn_t* h, int L, int row_lo, int row_hi, vsr_plan_t** out);   /* the decoder on model rows [row_lo, row_hi) only */
 int vsr_plan_create_box(const vsr_sttn_t* h, int L, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);   /* ... and columns */
-/* ... of L frames whose first n_ctx are read-only context (vsr_sttn_auto_chunk_ctx); works on a host-only handle like the others */
+/* ... of L frames whose first n_ctx are read-only context (vsr_sttn_auto_chunk_ctx, vsr_sttn_det_batch_ctx); works on a host-only handle like the others */
 int vsr_plan_create_ctx(const vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);
 int vsr_raft_plan_create(const vsr_raft_t* h, int t, int H, int W, int iters, vsr_plan_t** out);
 int vsr_rfc_plan_create(const vsr_rfc_t* h, int t, int H, int W, vsr_plan_t** out);

@@ -216,11 +216,13 @@ class SubtitleRemover:
         self.phase_seconds["windows, pass B: read + upload + YUV->BGR, inpainting, BGR->YUV + download + write"] = time.time() - t0
         return True
 
-    def _run_resident_jobs(self, jobs, plugin, clip, store=None):
+    def _run_resident_jobs(self, jobs, plugin, clip, store=None, look=None):
         """the independent batches of a resident run: one after the other, or over VSR_BATCH_LANES plugin instances (tools/batch_lanes.py).
         store: a tools/resident.StreamingStore -- with one lane the frames in front of the next batch are handed to it as each batch
         is enqueued (behind an event on the compute stream), so that they are converted, downloaded and written under the batches
-        that follow; jobs are slices of clip.frames in frame order."""
+        that follow; jobs are slices of clip.frames in frame order.
+        look: a tools/det_lookback.ResidentLookback over the same jobs -- batch j then runs as look.call(plugin, j), which copies the
+        source rows later batches look back at aside first (the copies are its own: nothing of them reaches the store)."""
         import torch
 
         from .tools import batch_lanes
@@ -229,14 +231,20 @@ class SubtitleRemover:
             self._lane_cache = {}
         plugins = batch_lanes.lane_plugins(plugin, batch_lanes.lanes_from_env(), self._lane_cache)
         if store is None or len(plugins) > 1 or os.environ.get("VSR_STREAM_STORE", "1") == "0":      # (0: everything is written after the last batch)
-            batch_lanes.run_jobs(jobs, plugins, clip.frames.device)
+            if look is not None:
+                batch_lanes.run_map(list(range(len(jobs))), plugins, look.call, clip.frames.device)
+            else:
+                batch_lanes.run_jobs(jobs, plugins, clip.frames.device)
             return
         dev = clip.frames.device
         frame_elems = clip.frames[0].numel()
         first = [(job[0].data_ptr() - clip.frames.data_ptr()) // frame_elems for job in jobs]     # first frame of every batch
         store.ready(first[0] if jobs else len(clip))
         for j, job in enumerate(jobs):
-            plugin(*job)
+            if look is not None:
+                look.call(plugin, j)
+            else:
+                plugin(*job)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))
             store.ready(first[j + 1] if j + 1 < len(jobs) else len(clip), ev)
@@ -415,14 +423,35 @@ class SubtitleRemover:
 
     def video_inpaint(self, tbar, model, text_detector=None):
         """backend/main.py:260-333 -- detector pass, interval construction, then `model(batch, mask)` per batch.
-        Frame numbers are 1-based here exactly as in the reference."""
+        Frame numbers are 1-based here exactly as in the reference.
+
+        Two options that are not the reference's, both off by default (then every job, every plugin call and every byte are what
+        they were) and read only for a plugin that takes context frames (sttn-det; lama and opencv ignore them): --scene-split cuts
+        every interval at the scene starts, --sttn-context N lets every batch look back at the N source frames in front of it inside
+        its piece (tools/det_lookback.py holds the definition).  One process, no resident windows."""
+        from .tools import det_lookback
+
+        max_load = config.getSttnMaxLoadNum()
+        n_context, scene_split = (0, False)
+        if getattr(model, "accepts_context", False):
+            n_context, scene_split = det_lookback.lookback_options(max_load)           # bad values: before any frame is read
+        lookback = bool(n_context or scene_split)
         dist = self._distributed()
+        if lookback and dist is not None:
+            raise RuntimeError("sttn-det context frames / scene-bounded intervals run in one process: a batch looks back at its predecessor's "
+                               f"frames, which another rank holds (world size {dist.get_world_size()}); run without them or on one GPU")
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), model)
-        detector = SubtitleDetect(self.video_path, self.sub_areas, text_detector=text_detector)
         on_device = getattr(model, "accepts_device_frames", False)
+        wclip = self._open_windowed() if lookback and on_device else None      # (the header only: no frame is read)
+        if wclip is not None:
+            raise RuntimeError("sttn-det context frames / scene-bounded intervals do not run in resident windows (--resident-windows on a clip "
+                               "over VSR_RESIDENT_GB): a batch looks back across window boundaries; run without them, without "
+                               "--resident-windows, or with a larger VSR_RESIDENT_GB")
+        detector = SubtitleDetect(self.video_path, self.sub_areas, text_detector=text_detector)
         resident = self._open_resident() if on_device else None
-        wclip = self._open_windowed() if on_device and resident is None else None
+        if not lookback:                                           # (with an option on, the answer is in: not a windowed run)
+            wclip = self._open_windowed() if on_device and resident is None else None
         sub_list, wclip = self._find_subtitles(detector, resident[0] if resident is not None else None, wclip)
         if len(sub_list) == 0:
             self._run_items(tbar, (), model)
@@ -432,6 +461,16 @@ class SubtitleRemover:
                                      config.subtitleTimelineForwardFrameCount.value)
         ranges = detector.filter_and_merge_intervals(ranges, config.sttnReferenceLength.value)
         start_end = {s: min(e, self.frame_count) for s, e in ranges}
+        cuts = []
+        if scene_split:
+            # one scene pass (the call propainter_mode makes: the cuts pinned to the reference's SceneManager), over the resident clip
+            # when there is one; its numbers are 1-based
+            dev = self.device
+            points = self._timed("scene cuts", detector.get_scene_div_frame_no, self.video_path,
+                                 device=int(dev.split(":")[1]) if isinstance(dev, str) and ":" in dev else 0,
+                                 **self._clip_kw(resident[0] if resident is not None else None))
+            cuts = [int(p) - 1 for p in points]
+        self.scene_cuts = cuts
 
         def interval_mask(first, last):
             coords = []
@@ -468,6 +507,12 @@ class SubtitleRemover:
             clip, wf = resident
 
             def inpaint_all():
+                if lookback:
+                    # (the source rows a later batch looks back at are copied aside before their batch is inpainted: ResidentLookback)
+                    jobs = det_lookback.det_jobs(start_end, len(clip), interval_mask, cuts, n_context, max_load)
+                    self._run_resident_jobs([(clip.frames[lo:hi], mask) for lo, hi, _, mask in jobs], model, clip, store,
+                                            det_lookback.ResidentLookback(clip.frames, jobs) if n_context else None)
+                    return
                 jobs = [(clip.frames[lo:hi], mask) for lo, hi, mask in index_jobs(len(clip))]
                 self._run_resident_jobs(jobs, model, clip, store)
 
@@ -482,6 +527,18 @@ class SubtitleRemover:
             self._timed("BGR->YUV + download + write (what is left after the last batch)", store.finish)
             return
         reader = open_video(self.video_path)
+        process = model
+        if n_context:
+            # host frames: a batch's context goes along with its work item, in front of the batch's frames (they are still the source's
+            # here); how many of an item's frames are context waits in a queue that items() fills and the plugin call empties, both in
+            # item order (one process: tools/batch_parallel.py hands the items to `process` one by one, as they come)
+            import collections
+
+            n_ctx_of = collections.deque()
+
+            def process(frames, mask):
+                k = n_ctx_of.popleft()
+                return model(frames[k:], mask, context=frames[:k])
 
         def items():
             idx = 0
@@ -502,12 +559,20 @@ class SubtitleRemover:
                     idx += 1
                     frames.append(frame)
                 mask = interval_mask(first, last)
+                if lookback:
+                    for lo, hi, ctx_lo in det_lookback.piece_jobs(first - 1, first - 1 + len(frames), cuts, n_context, max_load):
+                        if n_context:
+                            n_ctx_of.append(lo - ctx_lo)
+                        yield ("work", frames[ctx_lo - (first - 1):hi - (first - 1)], mask)
+                    continue
                 for batch in batch_generator(frames, config.getSttnMaxLoadNum()):
                     if len(batch) >= 1:
                         yield ("work", batch, mask)
 
         try:
-            self._timed("read + inpainting + write (host frames)", self._run_items, tbar, items(), model)
+            self._timed("read + inpainting + write (host frames)", self._run_items, tbar, items(), process)
+            if n_context and n_ctx_of:
+                raise RuntimeError(f"sttn-det look-back: {len(n_ctx_of)} work items were made and never inpainted")
         finally:
             reader.release()
 

@@ -23,12 +23,14 @@ def build_parser():
     # not in the reference: a clip over VSR_RESIDENT_GB stays on the GPU as a sequence of resident windows (sets VSR_IO_RESIDENT=windows)
     parser.add_argument("--resident-windows", action="store_true",
                         help="a *.y4m clip too large for VSR_RESIDENT_GB runs as HBM-resident windows instead of the host-frame loop")
-    # not in the reference: sttn-auto chunks restart at scene cuts / look back at the source frames in front of them
+    # not in the reference: sttn-auto chunks / sttn-det intervals restart at scene cuts and look back at the source frames in front of them
     parser.add_argument("--scene-split", action="store_true",
-                        help="sttn-auto: no chunk straddles a scene cut (one scene-detection pass over the video first); sets VSR_SCENE_SPLIT=1")
+                        help="sttn-auto, sttn-det: no chunk / batch straddles a scene cut (one scene-detection pass over the video first); "
+                             "sets VSR_SCENE_SPLIT=1")
     parser.add_argument("--sttn-context", type=int, default=None, metavar="N",
-                        help="sttn-auto: every chunk also sees the N source frames in front of it (0 <= N <= the chunk length, "
-                             "never across a scene cut with --scene-split); sets VSR_STTN_CONTEXT")
+                        help="sttn-auto, sttn-det: every chunk / batch also sees the N source frames in front of it (0 <= N <= the chunk "
+                             "length / the batch limit; never across a scene cut with --scene-split, sttn-det: never in front of its "
+                             "subtitle interval); sets VSR_STTN_CONTEXT")
     return parser
 
 

@@ -61,9 +61,10 @@ def context_span(piece_start, scene_start, n_context):
     return max(piece_start - int(n_context), scene_start), piece_start
 
 
-def lookback_options(context, scene_split, clip_gap, env=None):
+def lookback_options(context, scene_split, clip_gap, env=None, what="sttn-auto", bound="clip_gap"):
     """(n_context, scene_split) of an sttn-auto run: the constructor's arguments, None = the environment (VSR_STTN_CONTEXT, an
-    integer; VSR_SCENE_SPLIT=1).  Off by default.  ValueError for a context that is no integer in [0, clip_gap]."""
+    integer; VSR_SCENE_SPLIT=1).  Off by default.  ValueError for a context that is no integer in [0, clip_gap].
+    (what / bound: the words of the error message -- sttn-det reads the same two variables, tools/det_lookback.lookback_options.)"""
     import os
 
     env = os.environ if env is None else env
@@ -76,9 +77,9 @@ def lookback_options(context, scene_split, clip_gap, env=None):
         if isinstance(context, float) and n != context:
             raise ValueError
     except (TypeError, ValueError):
-        raise ValueError(f"sttn-auto context: {context!r} is not an integer") from None
+        raise ValueError(f"{what} context: {context!r} is not an integer") from None
     if n < 0 or n > int(clip_gap):
-        raise ValueError(f"sttn-auto context: {n} frames asked for, 0 <= N <= clip_gap = {int(clip_gap)} are possible")
+        raise ValueError(f"{what} context: {n} frames asked for, 0 <= N <= {bound} = {int(clip_gap)} are possible")
     return n, bool(scene_split)
 
 

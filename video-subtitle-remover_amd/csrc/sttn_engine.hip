@@ -864,7 +864,7 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
     const Geometry& g = h->model.g;
     const int mw = g.modelW, mh = g.modelH;
     const int Ls = (sel && nsel > 0) ? nsel : L;
-    // look-back context (vsr_sttn_auto_chunk_ctx): the plan's list is the nCtx context frames followed by the Ls selected ones; the
+    // look-back context (vsr_sttn_auto_chunk_ctx, vsr_sttn_det_batch_ctx): the plan's list is the nCtx context frames followed by the Ls selected ones; the
     // context strips are resized in front of them, the blend reads the comp frames behind them and writes frames_dev alone
     const int Lp = nCtx + Ls;
     const int32_t* dSel = nullptr;
@@ -950,8 +950,8 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
         if (vsr_launch_resize_u8(frames_dev + (int64_t)ymin * W * 3, frameStride, W * 3, W, sh, (uint8_t*)h->bufs[BUF_IN_U8] + (int64_t)nCtx * mh * mw * 3, mw,
                                  mh, Ls, 3, dSel, st->dxofs, st->dialpha, st->dyofs, st->dibeta, stream) != 0)
             return fail(VSR_ERR_HIP, "resize launch failed");
-        if (det) // cv2.resize(mask_crop, (432, 240)) -- the same strip mask for every frame (frame stride 0)
-            if (vsr_launch_resize_u8(mask_dev + (int64_t)ymin * W, 0, W, W, sh, (uint8_t*)h->bufs[BUF_MASK_U8], mw, mh, Ls, 1,
+        if (det) // cv2.resize(mask_crop, (432, 240)) -- the same strip mask for every frame of the list, context included (frame stride 0)
+            if (vsr_launch_resize_u8(mask_dev + (int64_t)ymin * W, 0, W, W, sh, (uint8_t*)h->bufs[BUF_MASK_U8], mw, mh, Lp, 1,
                                      nullptr, st->dxofs, st->dialpha, st->dyofs, st->dibeta, stream) != 0)
                 return fail(VSR_ERR_HIP, "mask resize launch failed");
         if (k > 0 || attempt > 0) RCCHK(build_plan_dev(h, Lp, attempt ? 0 : h->precision, &pd, decLo[k], decHi[k], decXLo[k], decXHi[k], nCtx));
@@ -1115,6 +1115,17 @@ int vsr_sttn_det_batch_box(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int
     RCCHK(need_gpu(h));
     if (h->model.g.variant != VSR_VARIANT_STTN_DET) return fail(VSR_ERR_STATE, "not an sttn-det model");
     return strips_common(h, true, frames_dev, L, H, W, mask_dev, n_areas, areas, nullptr, 0, (hipStream_t)stream_, mask_rows, mask_cols);
+}
+
+int vsr_sttn_det_batch_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
+                           const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const uint8_t* ctx_dev, int n_ctx,
+                           void* stream_)
+{
+    RCCHK(need_gpu(h));
+    if (h->model.g.variant != VSR_VARIANT_STTN_DET) return fail(VSR_ERR_STATE, "not an sttn-det model");
+    if (n_ctx < 0 || (n_ctx > 0 && !ctx_dev)) return fail(VSR_ERR_ARG, "bad context");
+    return strips_common(h, true, frames_dev, L, H, W, mask_dev, n_areas, areas, nullptr, 0, (hipStream_t)stream_, mask_rows, mask_cols,
+                         n_ctx > 0 ? ctx_dev : nullptr, n_ctx);
 }
 
 int vsr_sttn_set_precision(vsr_sttn_t* h, int mode)

@@ -967,7 +967,6 @@ Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, i
     if (!model.packed_ready()) throw std::runtime_error("model weights are not packed");
     if (L <= 0) throw std::runtime_error("empty frame list");
     if (nCtx < 0 || nCtx >= L) throw std::runtime_error("context frames: 0 <= n_ctx < frames of the list");
-    if (nCtx > 0 && g.variant != 0) throw std::runtime_error("context frames are an sttn-auto option");
     bufElems.assign(BUF_COUNT, 0);
     bufElems[BUF_WEIGHTS] = (int64_t)model.packed.size();
     const int mh = g.modelH, mw = g.modelW, fh = g.featH, fw = g.featW, C = g.channels;

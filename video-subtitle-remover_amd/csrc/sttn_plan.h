@@ -199,10 +199,13 @@ public:
     // only where the mask is set: vsr_sttn_auto_chunk) -- the decoder computes those rows and what they depend on, nothing else
     // (buildWindow); decHi <= decLo = the whole image
     // decXLo / decXHi: the same for columns (the GEMMs take rectangles; the two elementwise kernels of the decoder keep whole rows)
-    // nCtx: the first nCtx frames of the list are look-back CONTEXT (sttn-auto, vsr_sttn_auto_chunk_ctx): read by every window that
+    // nCtx: the first nCtx frames of the list are look-back CONTEXT (vsr_sttn_auto_chunk_ctx, vsr_sttn_det_batch_ctx): read by every window that
     // holds them -- as neighbours and as reference frames, at the positions a plain plan of L frames gives them -- and never written:
     // the last block's query rows, the decoder and the running average in BUF_COMP are built for the other ("written") neighbours of a
     // window only, and a window without one is not built at all.  The written frames come out with the bits of the plain plan of L.
+    // sttn-det needs no op of its own for this: its three extras index frames by LIST index -- enc.im2col pre-masks frame f with mask
+    // plane f of BUF_MASK_U8 (sized for the whole list), dec.out blends comp frame tFrameIdx[i] with input frame and mask plane
+    // tFrameIdx[i] over every row -- and the decode ops' frame tables name written frames only.
     Plan(const Model& model, int L, int precision = 0, int lanes = 1, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0, int nCtx = 0);
     // the bounds a plan with these arguments decodes: clipped to the image and widened to whole blocks of the output conv (all 0 = the
     // whole image: no promise, or the per-pixel form of the output conv).  Needs no plan: vsr_sttn_decode_rows asks once per area.

@@ -361,19 +361,35 @@ class SttnEngine(AccuracyGuard):
                                            C.c_void_p(comp.data_ptr()), counts.ctypes.data_as(C.c_void_p), _stream_ptr()))
         return comp, counts
 
-    def det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None):
+    def det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None, context=None):
         """STTNDetInpaint.__call__ on one batch, in place on frames_dev uint8 [L,H,W,3] BGR; mask_dev raw 0/255 [H,W].  The rows of
         every strip that hold the mask go along (mask_rows): the decoder computes only the model rows the prediction is taken from
-        (vsr_sttn_det_batch_rows) -- same frames; decode_rows=False: no promise."""
-        return self._guarded_in_place(lambda t: self._det_batch(t, mask_dev, areas, decode_rows, mask_host), frames_dev)
+        (vsr_sttn_det_batch_rows) -- same frames; decode_rows=False: no promise.
+        context (not in the reference): uint8 [n_ctx,H,W,3] on the device, the source frames in front of the batch.  The batch comes
+        out as the last L frames of the list context ++ frames would, bit for bit; the context tensor is only read (and is the
+        same tensor in the accuracy guard's exact re-run: the guard clones and compares frames_dev alone)."""
+        return self._guarded_in_place(lambda t: self._det_batch(t, mask_dev, areas, decode_rows, mask_host, context), frames_dev)
 
-    def _det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None):
+    def _det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None, context=None):
         assert frames_dev.dtype == torch.uint8 and frames_dev.is_cuda and frames_dev.is_contiguous()
         assert mask_dev.dtype == torch.uint8 and mask_dev.is_cuda and mask_dev.is_contiguous()
         L, H, W, _ = frames_dev.shape
         ar = np.ascontiguousarray(np.asarray(areas, dtype=np.int32).reshape(-1, 4))
         self._check_mask_host(mask_host, mask_dev)
         rows = np.ascontiguousarray(self.mask_rows(mask_dev if mask_host is None else mask_host, ar)) if decode_rows else np.zeros((ar.shape[0], 2), dtype=np.int32)
+        if context is not None:      # (an empty one too: n_ctx = 0 is the entry point's plain call)
+            assert context.dtype == torch.uint8 and context.is_cuda and context.is_contiguous() and context.device == frames_dev.device
+            if tuple(context.shape[1:]) != (H, W, 3):
+                raise ValueError(f"context frames {tuple(context.shape[1:])} do not have the batch's geometry {(H, W, 3)}")
+            cols = None
+            if decode_rows and switches.on("VSR_DECODE_COLS"):
+                cols = np.ascontiguousarray(self.mask_cols(mask_dev if mask_host is None else mask_host, ar))
+            with torch.cuda.device(frames_dev.device):
+                check(lib.vsr_sttn_det_batch_ctx(self._h, C.c_void_p(frames_dev.data_ptr()), L, H, W, C.c_void_p(mask_dev.data_ptr()),
+                                                 ar.shape[0], ar.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+                                                 None if cols is None else cols.ctypes.data_as(C.c_void_p),
+                                                 C.c_void_p(context.data_ptr()), int(context.shape[0]), _stream_ptr()))
+            return frames_dev
         if decode_rows and switches.on("VSR_DECODE_COLS"):
             cols = np.ascontiguousarray(self.mask_cols(mask_dev if mask_host is None else mask_host, ar))
             with torch.cuda.device(frames_dev.device):
