@@ -624,6 +624,21 @@ int vsr_io_bgr_to_planes(const uint8_t* bgr_dev, int H, int W, int chroma_w, int
                          int64_t frame_bytes, int nframes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Seam feather (--seam-feather F, csrc/feather_kernels.hip; the statement is tests/_feather_statement.py, the design DESIGN.md 4.11):
+ * the mask-exact, feathered composite a plugin call can end with.  Stateless; all pointers are device pointers.
+ * ------------------------------------------------------------------------------------- */
+/* cmask_dev uint8 [H][W] (non-zero: the plugin blends its prediction here) -> alpha_dev uint8 [H][W]: d = min(feather, Chebyshev
+ * distance to the nearest pixel of the frame with cmask == 0); 0 outside the mask, no ramp along the frame border.  1 <= feather <= 64. */
+int vsr_feather_alpha(const uint8_t* cmask_dev, int H, int W, int feather, uint8_t* alpha_dev, void* stream);
+/* frames_dev: n frames uint8 [H][W][3] holding the fill, frame f at frames_dev + f * frame_stride bytes, composited IN PLACE with the
+ * source frames at src_dev + f * src_frame_stride (any alignment, strides >= H * W * 3) under alpha_dev = d of vsr_feather_alpha:
+ * d == feather: untouched; d == 0: the source byte; else (d * fill + (feather - d) * src + feather / 2) / feather.
+ * Bad arguments (a null pointer, H or W <= 0, H * W * 3 >= 2^31, feather outside 1..64, a stride smaller than a frame, n < 0) return VSR_ERR_ARG and
+ * launch nothing; n == 0 is success without a launch. */
+int vsr_feather_composite(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride,
+                          const uint8_t* alpha_dev, int n, int H, int W, int feather, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),
  * with symbolic buffers and the offset tables -- replayed on the CPU by tests/.
  * ------------------------------------------------------------------------------------- */

@@ -220,6 +220,8 @@ SIGNATURES = {
     "vsr_telea_plan_tmap": (_I, [_P, _P]),
     "vsr_telea_plan_weights": (_I, [_P, _P, _P]),
     "vsr_telea_inpaint": (_I, [_P, _P, _L, _I, _P]),
+    "vsr_feather_alpha": (_I, [_P, _I, _I, _I, _P, _P]),
+    "vsr_feather_composite": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P]),
     "vsr_plan_consts": (_L, [_P, _P, _L]),
     "vsr_plan_destroy": (None, [_P]),
     "vsr_plan_num_buffers": (_I, [_P]),

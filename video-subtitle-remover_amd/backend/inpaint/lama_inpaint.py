@@ -13,6 +13,7 @@ with torch.jit.load (its parameters are read, the module is never executed).  Th
 import numpy as np
 import torch
 
+from ..tools import seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask
 from ...engine import LamaEngine
 from .sttn_auto_inpaint import _device_index
@@ -60,7 +61,24 @@ class LamaInpaint:
     def close(self):
         self.engine.close()
 
+    def composite_mask(self, input_mask):
+        """uint8 [H,W]: the pixels this plugin blends its prediction under (--seam-feather, tools/seam_feather.py): mask != 0"""
+        m = np.asarray(input_mask)
+        return (m.reshape(m.shape[0], m.shape[1]) != 0).astype(np.uint8)
+
     def inpaint(self, image, mask):
+        """the single picture and propainter's single frames (main.py:217-224,364); under --seam-feather a one-frame plugin call"""
+        return seam_feather.plugin_call(self, self._inpaint_one, [image], mask, self.engine.device)[0]
+
+    def _inpaint_one(self, frames, mask):
+        """the body of inpaint() as a plugin call on one frame: [image] -> [filled image], or a device tensor [1,H,W,3] in place"""
+        if not isinstance(frames, torch.Tensor):
+            return [self._inpaint(frames[0], mask)]
+        msk = np.asarray(mask)
+        msk = torch.from_numpy(np.ascontiguousarray(msk.reshape(msk.shape[0], msk.shape[1]))).to(frames.device)
+        return self.engine.inpaint(frames, msk, out=frames)
+
+    def _inpaint(self, image, mask):
         img = np.ascontiguousarray(np.array(image))
         msk = np.array(mask)
         if msk.ndim == 3:
@@ -71,7 +89,7 @@ class LamaInpaint:
 
     def _inpaint_batch(self, images, masks):
         if len(images) == 1:
-            return [self.inpaint(images[0], masks[0])]
+            return [self._inpaint(images[0], masks[0])]
         dev = self.engine.device
         imgs = torch.from_numpy(np.ascontiguousarray(np.stack(images))).to(dev)
         msks = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(m).reshape(m.shape[0], m.shape[1]) for m in masks]))).to(dev)
@@ -83,6 +101,10 @@ class LamaInpaint:
         return [res[i] for i in range(res.shape[0])]
 
     def __call__(self, input_frames, input_mask):
+        """(--seam-feather: the call ends with the feathered composite, tools/seam_feather.py)"""
+        return seam_feather.plugin_call(self, self._call, input_frames, input_mask, self.engine.device)
+
+    def _call(self, input_frames, input_mask):
         mask = input_mask[:, :, None]
         H_ori, W_ori = mask.shape[:2]
         split_h = int(W_ori * 3 / 16)

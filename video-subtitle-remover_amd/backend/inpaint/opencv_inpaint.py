@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from ...engine import TeleaEngine
+from ..tools import seam_feather
 from .sttn_auto_inpaint import _device_index
 
 RADIUS = 3                                                                   # opencv_inpaint.py:9
@@ -63,10 +64,17 @@ class OpenCVInpaint:
     def inpaint(self, frame, mask):
         return self([frame], mask)[0]
 
+    def composite_mask(self, input_mask):
+        """uint8 [H,W]: the pixels this plugin fills (--seam-feather, tools/seam_feather.py): mask != 0"""
+        return (_mask2d(input_mask) != 0).astype(np.uint8)
+
     def __call__(self, input_frames, input_mask):
         """input_frames: the reference's list of HxWx3 uint8 BGR arrays (fresh arrays come back, inputs untouched), or -- the
         HBM-resident loop of main.SubtitleRemover, tools/resident.py -- a uint8 [n,H,W,3] device tensor, which is inpainted IN
-        PLACE and returned."""
+        PLACE and returned.  (--seam-feather: the call ends with the feathered composite, tools/seam_feather.py.)"""
+        return seam_feather.plugin_call(self, self._call, input_frames, input_mask, self.device)
+
+    def _call(self, input_frames, input_mask):
         mask = _mask2d(input_mask)
         if self._cv2 is not None:
             return [self._cv2.inpaint(f, mask, RADIUS, self._cv2.INPAINT_TELEA) for f in input_frames]

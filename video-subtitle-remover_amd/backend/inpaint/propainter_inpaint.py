@@ -22,6 +22,7 @@ import numpy as np
 import scipy.ndimage
 import torch
 
+from ..tools import seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask
 from ... import switches
 from ..._lib import check, lib
@@ -466,7 +467,22 @@ class PropainterInpaint:
             out = comp.cpu().numpy()                                                        # already BGR (:360)
         return [out[i] for i in range(n)]
 
+    def composite_mask(self, input_mask):
+        """uint8 [H,W]: the pixels this plugin blends its prediction under (--seam-feather, tools/seam_feather.py): per strip of
+        __call__ the dilated mask inpaint() blends with (read_mask(...)[1], the dilation bounded by the strip), put back at the
+        strip's position; the union over the strips"""
+        mask = np.asarray(input_mask)[:, :, None]
+        H_ori, W_ori = mask.shape[:2]
+        out = np.zeros((H_ori, W_ori), dtype=np.uint8)
+        for y0, y1, x0, x1 in get_inpaint_area_by_mask(W_ori, H_ori, int(W_ori * 3 / 16), mask, multiple=8):
+            out[y0:y1, x0:x1] |= read_mask(mask[y0:y1, x0:x1, :], 1, self.mask_dilation, self.mask_dilation)[1]
+        return out
+
     def __call__(self, input_frames, input_mask):
+        """(--seam-feather: the call ends with the feathered composite, tools/seam_feather.py)"""
+        return seam_feather.plugin_call(self, self._call, input_frames, input_mask, self.dev)
+
+    def _call(self, input_frames, input_mask):
         mask = input_mask[:, :, None]
         H_ori, W_ori = mask.shape[:2]
         split_h = int(W_ori * 3 / 16)

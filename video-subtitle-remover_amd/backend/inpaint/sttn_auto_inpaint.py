@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from ..config import config
+from ..tools import seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask, is_frame_number_in_ab_sections, threshold_mask
 from ..tools.video_io import ArrayWriter, device_bgr_to_planes, device_planes_to_bgr, open_video
 from ...engine import SttnEngine
@@ -59,6 +60,25 @@ class STTNInpaint:
                                  neighbor_stride=self.neighbor_stride, ref_length=self.ref_length)
         self.model_input_width, self.model_input_height = 640, 120
 
+    def composite_mask(self, input_mask, thresholded=False):
+        """uint8 [H,W] of the FULL frame: the pixels this plugin blends its prediction under (--seam-feather, tools/seam_feather.py):
+        the thresholded mask inside the rows of its inpaint areas.  thresholded: input_mask already is threshold_mask's [H,W,1]."""
+        mask = input_mask if thresholded else threshold_mask(input_mask)
+        H_ori, W_ori = mask.shape[:2]
+        out = np.zeros((H_ori, W_ori), dtype=np.uint8)
+        for y0, y1, _, _ in get_inpaint_area_by_mask(W_ori, H_ori, int(W_ori * 3 / 16), mask):
+            out[y0:y1] = mask[y0:y1, :, 0] != 0
+        return out
+
+    def auto_chunk(self, frames_dev, mask_dev, areas, cmask=None, rows=None, **kw):
+        """SttnEngine.auto_chunk, where all three chunk loops and __call__ end.  cmask: None (--seam-feather off: the engine call and
+        nothing else), or the full-frame composite mask; rows = (y_lo, y_hi): frames_dev holds these rows of the frames only, the
+        distance is taken on the full frame and sliced (tools/seam_feather.device_call).  Context frames (kw) are read-only."""
+        if cmask is None:
+            return self.engine.auto_chunk(frames_dev, mask_dev, areas, **kw)
+        return seam_feather.device_call(frames_dev, cmask, lambda t: self.engine.auto_chunk(t, mask_dev, areas, **kw),
+                                        seam_feather.feather_option(), rows=rows)
+
     def __call__(self, input_frames, input_mask):
         mask = threshold_mask(input_mask)
         H_ori, W_ori = mask.shape[:2]
@@ -69,7 +89,8 @@ class STTNInpaint:
         dev = self.engine.device
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(dev, non_blocking=True)
         dmask = torch.from_numpy(np.ascontiguousarray(mask[:, :, 0])).to(dev, non_blocking=True)
-        self.engine.auto_chunk(frames, dmask, inpaint_area, mask_host=mask[:, :, 0])
+        cmask = self.composite_mask(mask, thresholded=True) if seam_feather.feather_option() else None
+        self.auto_chunk(frames, dmask, inpaint_area, cmask=cmask, mask_host=mask[:, :, 0])
         out = frames.cpu().numpy()
         return [out[i] for i in range(out.shape[0])]
 
@@ -141,6 +162,7 @@ class STTNAutoInpaint:
         from ..tools import chunk_parallel as cp
 
         n_context, scene_split = cp.lookback_options(self.context, self.scene_split, self.clip_gap)      # bad values: before any frame is read
+        feather = seam_feather.refuse_ranks(dist)            # --seam-feather: one process (bad values and several ranks: before any frame is read)
         if (n_context or scene_split) and dist is not None:
             raise RuntimeError("sttn-auto context frames / scene-bounded chunks run in one process: a chunk looks back at its predecessor's "
                                f"frames, which another rank holds (world size {dist.get_world_size()}); run without them or on one GPU")
@@ -173,6 +195,8 @@ class STTNAutoInpaint:
         local_areas = [(a[0] - y_lo, a[1] - y_lo, a[2], a[3]) for a in inpaint_area]
         dmask = torch.from_numpy(np.ascontiguousarray(mask[y_lo:y_hi, :, 0])).to(engine.device) if inpaint_area else None
         mask_rows_host = mask[y_lo:y_hi, :, 0] if inpaint_area else None     # the engine reads the rows that hold the mask off this copy
+        # --seam-feather: the composite mask of the FULL frame; a loop that hands the engine strip rows says which (STTNInpaint.auto_chunk)
+        cmask = self.sttn_inpaint.composite_mask(mask, thresholded=True) if (feather and inpaint_area) else None
         kept = {}
 
         def tick(original, frame):
@@ -216,7 +240,8 @@ class STTNAutoInpaint:
                     look["saved"].copy_(rows[n - k:n])
             sel = [j - s for j in range(s, s + n) if is_frame_number_in_ab_sections(j, ab_sections)]
             if sel:
-                engine.auto_chunk(rows[:n], dmask, local_areas, sel=None if len(sel) == n else sel, mask_host=mask_rows_host, context=context)
+                self.sttn_inpaint.auto_chunk(rows[:n], dmask, local_areas, cmask=cmask, rows=(y_lo, y_hi), sel=None if len(sel) == n else sel,
+                                             mask_host=mask_rows_host, context=context)
 
         def store(i, rows):
             for j, frame in enumerate(kept.pop(i)):
@@ -230,7 +255,7 @@ class STTNAutoInpaint:
         if local is not None:
             # every rank reads and writes its own chunks by offset (tools/rank_io.py): no rank-0 funnel, no collective on the data path
             try:
-                self._run_rank_local(local, dist, rank, engine, ranges, mask, inpaint_area, (H_ori, W_ori), ab_sections, tick, frame_info["len"])
+                self._run_rank_local(local, dist, rank, engine, ranges, mask, inpaint_area, (H_ori, W_ori), ab_sections, tick, frame_info["len"], cmask)
             finally:
                 reader.release()
                 if writer:
@@ -296,7 +321,7 @@ class STTNAutoInpaint:
             return None
         return src, decision[0][0], rf, decision[0][1]
 
-    def _run_rank_local(self, local, dist, rank, engine, ranges, mask, inpaint_area, size, ab_sections, tick, total):
+    def _run_rank_local(self, local, dist, rank, engine, ranges, mask, inpaint_area, size, ab_sections, tick, total, cmask=None):
         """the chunk loop of _run with per-rank file access: chunk i's stored planes -> pinned -> HBM -> BGR (vsr_io_yuv_to_bgr) ->
         vsr_sttn_auto_chunk in place on the whole frames -> planes (vsr_io_bgr_to_yuv) -> pinned -> the sink, at the records' offsets"""
         from ..tools import rank_io
@@ -335,7 +360,7 @@ class STTNAutoInpaint:
                 device_planes_to_bgr(rf, d_in.data_ptr(), H, W, full.data_ptr(), k, cur())
                 sel = [j - s for j in range(s, s + k) if is_frame_number_in_ab_sections(j, ab_sections)]
                 if sel:
-                    engine.auto_chunk(full[:k], dmask, inpaint_area, sel=None if len(sel) == k else sel, mask_host=mask_host)
+                    self.sttn_inpaint.auto_chunk(full[:k], dmask, inpaint_area, cmask=cmask, sel=None if len(sel) == k else sel, mask_host=mask_host)
                 device_bgr_to_planes(wf, full.data_ptr(), H, W, d_out.data_ptr(), k, cur(), d_in.data_ptr(), rf, path="the by-offset chunk loop")
                 to.copy_(d_out[:k], non_blocking=True)
                 torch.cuda.current_stream(dev).synchronize()

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from ..config import config
+from ..tools import seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask
 from ...engine import SttnEngine
 from .sttn_auto_inpaint import _device_index, _load_state_dict
@@ -35,7 +36,16 @@ class STTNDetInpaint:
         """a second instance on the same device from the same checkpoint: its own engine and workspace (tools/batch_lanes.py)"""
         return STTNDetInpaint(self.device, self._model_path)
 
+    def composite_mask(self, input_mask):
+        """uint8 [H,W]: the pixels this plugin blends its prediction under (--seam-feather, tools/seam_feather.py): mask != 0"""
+        return (np.asarray(input_mask) != 0).astype(np.uint8)
+
     def __call__(self, input_frames, input_mask, context=None):
+        """The call below; under --seam-feather it ends with the feathered composite (tools/seam_feather.py): the batch comes back
+        mask-exact, the context frames are read-only as before and take no part."""
+        return seam_feather.plugin_call(self, self._call, input_frames, input_mask, self.engine.device, context=context)
+
+    def _call(self, input_frames, input_mask, context=None):
         """input_frames: the reference's list of HxWx3 uint8 BGR arrays (fresh arrays come back), or -- the HBM-resident loop of
         main.SubtitleRemover, tools/resident.py -- a contiguous uint8 [n,H,W,3] device tensor, which is inpainted IN PLACE and
         returned.

@@ -292,6 +292,9 @@ class SubtitleRemover:
             model_dir = os.environ.get("PROPAINTER_MODEL_DIR", os.path.join(os.path.dirname(__file__), "models", "propainter"))
             propainter_inpaint = PropainterInpaint(self.device, model_dir, config.propainterMaxLoadNum.value)
         dist = self._distributed()
+        from .tools import seam_feather
+
+        seam_feather.refuse_ranks(dist)                                                 # --seam-feather: bad values and several ranks, before any frame is read
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), propainter_inpaint)
         if single_frame_inpaint is None:
@@ -431,6 +434,9 @@ class SubtitleRemover:
         its piece (tools/det_lookback.py holds the definition).  One process, no resident windows."""
         from .tools import det_lookback
 
+        from .tools import seam_feather
+
+        seam_feather.refuse_ranks(self._distributed())                                  # --seam-feather: bad values and several ranks, before any frame is read
         max_load = config.getSttnMaxLoadNum()
         n_context, scene_split = (0, False)
         if getattr(model, "accepts_context", False):
@@ -648,7 +654,10 @@ class SubtitleRemover:
         return det
 
     def run(self):
+        from .tools import seam_feather
+
         start_time = time.time()
+        seam_feather.refuse_ranks(self._distributed())                   # --seam-feather: a bad value or several ranks fail before any work is done
         if self._video_writer is None and self.is_path:
             self._y4m_like()                                             # a sink that cannot be made fails before any work is done
         if len(self.sub_areas) == 0:
@@ -699,6 +708,8 @@ def main(argv=None):
         os.environ["VSR_SCENE_SPLIT"] = "1"
     if args.sttn_context is not None:
         os.environ["VSR_STTN_CONTEXT"] = str(args.sttn_context)
+    if args.seam_feather is not None:
+        os.environ["VSR_SEAM_FEATHER"] = str(args.seam_feather)
     sr = SubtitleRemover(args.input)
     sr.sub_areas = [tuple(c) for c in args.subtitle_area_coords]
     if args.output is not None:

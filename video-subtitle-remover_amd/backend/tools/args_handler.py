@@ -31,11 +31,23 @@ def build_parser():
                         help="sttn-auto, sttn-det: every chunk / batch also sees the N source frames in front of it (0 <= N <= the chunk "
                              "length / the batch limit; never across a scene cut with --scene-split, sttn-det: never in front of its "
                              "subtitle interval); sets VSR_STTN_CONTEXT")
+    # not in the reference: every mode ends its plugin call with a mask-exact, feathered composite (tools/seam_feather.py)
+    parser.add_argument("--seam-feather", type=int, default=None, metavar="F",
+                        help="every mode: outside the pixels a plugin blends under, the written frame is the source bit for bit; inside, "
+                             "the fill ramps in over F pixels (1 = hard composite, 0 = off, at most 64); one process; sets VSR_SEAM_FEATHER")
     return parser
 
 
 def parse_args(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.seam_feather is not None:
+        from .seam_feather import feather_option
+
+        try:
+            feather_option(args.seam_feather)
+        except ValueError as e:
+            parser.error(f"--seam-feather: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

@@ -1,0 +1,174 @@
+"""--seam-feather F: the mask-exact, feathered composite every inpaint mode can end its plugin call with (not in the reference; opt-in,
+DESIGN 4.11; the numpy statement is tests/_feather_statement.py).
+
+For one plugin call on frames [n,H,W,3]:   src   the frames as they came in
+                                           fill  what the call returns with the option off
+                                           C     the plugin's composite mask, uint8 [H,W]: plugin.composite_mask(input_mask)
+                                           d(p)  min(F, Chebyshev distance from p to the nearest q inside the frame with C[q] == 0)
+    out[p] = (d(p) * fill[p] + (F - d(p)) * src[p] + F // 2) // F           per channel, integers
+d = 0 gives the source bit for bit, d = F the fill; F = 1 is the hard composite at full resolution, F >= 2 ramps the fill in over F
+pixels.  The frame border is no zero of C: a band that touches the bottom edge is not feathered there.
+
+F = 0 (the default) is OFF: the plugin's body runs as it always has -- no clone, no launch, no byte written that was not before.
+The option is read here and nowhere else (feather_option: --seam-feather sets VSR_SEAM_FEATHER).  The helper sits inside the plugin
+call, so every loop that ends in one (host frames, the HBM-resident clip, resident windows, batch lanes, the single picture,
+propainter's single-frame LaMa) gets it without knowing.  With F > 0, a non-empty C and n > 0 a call
+
+    1. takes d from the cache (vsr_feather_alpha once per (mask bytes, F); the last few are kept, as TeleaEngine keeps its plans),
+    2. clones the frames on the caller's stream,
+    3. runs the body unchanged,
+    4. launches vsr_feather_composite on the same stream, which the body's result is ordered on.
+
+The list form uploads once, runs the device form and downloads once.  Several ranks are refused (refuse_ranks) before any work.
+"""
+import collections
+import ctypes as C
+import os
+import threading
+
+import numpy as np
+
+MAX_FEATHER = 64
+ENV = "VSR_SEAM_FEATHER"
+MAX_ALPHAS = 4              # alphas kept per process: an interval's batches and the lanes present the same mask again and again
+
+
+def feather_option(value=None, env=None):
+    """F of this run: `value`, None = the environment (VSR_SEAM_FEATHER, unset or empty = 0 = off).  The one reading of the option.
+    ValueError for anything that is no integer in [0, 64]."""
+    env = os.environ if env is None else env
+    if value is None:
+        value = env.get(ENV, "0") or "0"
+    try:
+        f = int(value)
+        if isinstance(value, float) and f != value:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"seam feather: {value!r} is not an integer") from None
+    if f < 0 or f > MAX_FEATHER:
+        raise ValueError(f"seam feather: F = {f} asked for, 0 <= F <= {MAX_FEATHER} are possible (0 = off)")
+    return f
+
+
+def refuse_ranks(dist, feather=None):
+    """-> F.  With F > 0, more than one rank raises before any work: the frames of a call and its source clone live on the rank that
+    runs the call, and the ranks' writers have not been taught the option (the precedent of --sttn-context)."""
+    f = feather_option(feather)
+    if f and dist is not None and dist.get_world_size() > 1:
+        raise RuntimeError(f"--seam-feather / {ENV} = {f} runs in one process (world size {dist.get_world_size()}): "
+                           "run without it or on one GPU")
+    return f
+
+
+_alphas = collections.OrderedDict()         # (device index, H, W, F, mask bytes) -> uint8 [H,W] device tensor; least recently used first
+_lock = threading.Lock()
+stats = {"alpha_builds": 0, "alpha_hits": 0, "composites": 0}
+
+
+def alpha(cmask, feather, device):
+    """d of the composite mask `cmask` (host uint8 [H,W], non-zero = inside) on `device`: cached, or computed now by
+    vsr_feather_alpha.  The computing stream is waited for once, so that any stream (another lane's) may read the cached tensor."""
+    import torch
+
+    from ..._lib import check, lib
+
+    cmask = np.ascontiguousarray(cmask, dtype=np.uint8)
+    assert cmask.ndim == 2, "composite mask must be [H, W]"
+    device = torch.device(device)
+    H, W = cmask.shape
+    key = (device.index or 0, H, W, int(feather), cmask.tobytes())
+    with _lock:
+        d = _alphas.pop(key, None)
+        if d is None:
+            with torch.cuda.device(device):
+                c_dev = torch.from_numpy(cmask).to(device)
+                d = torch.empty((H, W), dtype=torch.uint8, device=device)
+                stream = torch.cuda.current_stream(device)
+                check(lib.vsr_feather_alpha(C.c_void_p(c_dev.data_ptr()), H, W, int(feather), C.c_void_p(d.data_ptr()),
+                                            C.c_void_p(stream.cuda_stream)))
+                stream.synchronize()
+            stats["alpha_builds"] += 1
+            while len(_alphas) >= MAX_ALPHAS:
+                _alphas.popitem(last=False)
+        else:
+            stats["alpha_hits"] += 1
+        _alphas[key] = d
+    return d
+
+
+def composite(frames, src, d, feather):
+    """in place on `frames` (uint8 [n,H,W,3] on the GPU, every frame contiguous; it holds the fill) with the source frames `src` (same
+    shape, its own frame stride) under d (uint8 [H,W] device): vsr_feather_composite on the current stream"""
+    import torch
+
+    from ..._lib import check, lib
+
+    n, H, W, _ = frames.shape
+    if n == 0:
+        return frames
+    for t in (frames, src):
+        assert t.dtype == torch.uint8 and t.is_cuda and tuple(t.shape) == (n, H, W, 3)
+        assert t.stride(3) == 1 and t.stride(2) == 3 and t.stride(1) == 3 * W, "every frame must be contiguous [H,W,3]"
+    assert d.dtype == torch.uint8 and d.is_contiguous() and tuple(d.shape) == (H, W) and d.device == frames.device == src.device
+    fs = frames.stride(0) if n > 1 else H * W * 3
+    ss = src.stride(0) if n > 1 else H * W * 3
+    with torch.cuda.device(frames.device):
+        stream = torch.cuda.current_stream(frames.device)
+        d.record_stream(stream)              # (a cached tensor, made on whichever stream asked first)
+        check(lib.vsr_feather_composite(C.c_void_p(frames.data_ptr()), fs, C.c_void_p(src.data_ptr()), ss, C.c_void_p(d.data_ptr()),
+                                        n, H, W, int(feather), C.c_void_p(stream.cuda_stream)))
+    stats["composites"] += 1
+    return frames
+
+
+def device_call(frames, cmask, body, feather, rows=None):
+    """body(frames) inpaints the device tensor `frames` in place (today's call); with F > 0 and a non-empty composite mask the frames
+    come back as the definition's.  cmask: the FULL-frame composite mask (host uint8) or a callable that makes it; rows = (y_lo, y_hi):
+    `frames` holds these rows of the frame only (sttn-auto's strip rows) -- d is computed on the full frame and sliced, so a mask that
+    touches the first or last of the rows ramps as it does in the whole frame."""
+    if not feather or frames.shape[0] == 0:
+        return body(frames)
+    cm = cmask() if callable(cmask) else cmask
+    if not cm.any():
+        return body(frames)
+    import torch
+
+    d = alpha(cm, feather, frames.device)
+    if rows is not None:
+        d = d[rows[0]:rows[1]]
+    src = frames.clone(memory_format=torch.contiguous_format)
+    out = body(frames)
+    composite(frames, src, d, feather)
+    return frames if out is None else out
+
+
+def plugin_call(plugin, body, input_frames, input_mask, device, context=None):
+    """The __call__ of a plugin under the option: body(input_frames, input_mask[, context=]) is the plugin's call as it has always
+    been (a list of HxWx3 arrays -> fresh arrays; a uint8 [n,H,W,3] device tensor -> inpainted in place and returned).
+    plugin.composite_mask(input_mask) names the pixels it blends under; device: where the list form uploads to."""
+    kw = {} if context is None else {"context": context}
+    f = feather_option()
+    if not f:
+        return body(input_frames, input_mask, **kw)
+    import torch
+
+    if isinstance(input_frames, torch.Tensor):
+        return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda t: body(t, input_mask, **kw), f)
+    if len(input_frames) == 0:
+        return body(input_frames, input_mask, **kw)
+    cm = plugin.composite_mask(input_mask)
+    if not cm.any():
+        return body(input_frames, input_mask, **kw)
+    if not getattr(plugin, "accepts_device_frames", False):
+        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the composite
+        fill = body(input_frames, input_mask, **kw)
+        frames = torch.from_numpy(np.ascontiguousarray(np.stack(fill))).to(device)
+        src = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
+        composite(frames, src, alpha(cm, f, frames.device), f)
+    else:
+        frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
+        if context is not None and len(context):
+            kw = {"context": torch.from_numpy(np.ascontiguousarray(np.stack(context))).to(device)}
+        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f)
+    out = frames.cpu().numpy()
+    return [out[i] for i in range(out.shape[0])]
