@@ -166,7 +166,7 @@ int vsr_sttn_det_batch_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int
  * reduced-precision mode (and every 256th) in mode 0 as well and demotes the handle when they differ by more than 50 dB.  A caller
  * that binds this ABI directly and uses modes 1-3 should do the same with its first chunk. */
 /* how THIS library instance reads one of its process-wide switches (read once, at first use): "VSR_DECODE_ROWS", "VSR_DECODE_COLS",
- * "VSR_QKV0_SHARED", "VSR_TRIM_LAST_BLOCK" -> 0 / 1, anything else -> -1.  The Python side (vsr_amd/switches.py) asserts that both agree. */
+ * "VSR_QKV0_SHARED", "VSR_TRIM_LAST_BLOCK", "VSR_SKIP_PAD_TAPS" -> 0 / 1, anything else -> -1.  The Python side (vsr_amd/switches.py) asserts that both agree. */
 int vsr_switch_state(const char* name);
 int vsr_sttn_set_precision(vsr_sttn_t* h, int mode);
 int64_t vsr_sttn_fallbacks(const vsr_sttn_t* h);
@@ -715,6 +715,9 @@ int vsr_plan_op_gemm(const vsr_plan_t* p, int i, int j, VsrGemmInfo* out);
 int vsr_plan_op_softmax(const vsr_plan_t* p, int i, int j, VsrSoftmaxInfo* out);
 int vsr_plan_counts(const vsr_plan_t* p, int32_t* counts);
 double vsr_plan_flops(const vsr_plan_t* p);
+/* what the plan's GEMMs contract: vsr_plan_flops without the products of a 3x3 conv that only read the zero halo above / below the
+ * image and are left out (VSR_SKIP_PAD_TAPS, default 1); equal to vsr_plan_flops for a plan that leaves nothing out */
+double vsr_plan_flops_executed(const vsr_plan_t* p);
 
 #ifdef __cplusplus
 }

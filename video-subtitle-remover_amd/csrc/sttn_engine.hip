@@ -75,6 +75,7 @@ struct OpDev {
     const float* lsum = nullptr; // reduce_scatter of a fused attention: partial row sums [nsplit][ldL]
     int ldL = 0;
     double flops = 0;
+    double flopsExec = 0;        // what the launch contracts (Op::flopsExecuted): the kernel records' count
     int lane = 0;                // stream the op is issued on (Plan::lanes)
     std::string tag;
 };
@@ -109,7 +110,7 @@ struct StripTables { // cv2.resize tables for one (W, split_h): down to model si
 
 struct TimingRec {
     std::string tag, kernel;
-    double flops;
+    double flops, flopsExec;     // the op tag's record takes the algorithmic count, the kernel's what the launch contracted
     hipEvent_t a, b;
 };
 
@@ -288,7 +289,7 @@ static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int 
     size_t cursor = 0;
     for (const Op& op : P.ops) {
         OpDev od;
-        od.kind = op.kind; od.tileCfg = op.tileCfg; od.bmode = op.bmode; od.flops = op.flops; od.tag = op.tag; od.lane = op.lane;
+        od.kind = op.kind; od.tileCfg = op.tileCfg; od.bmode = op.bmode; od.flops = op.flops; od.flopsExec = op.flopsExecuted >= 0 ? op.flopsExecuted : op.flops; od.tag = op.tag; od.lane = op.lane;
         if (op.kind == OP_GEMM) {
             std::vector<GGProblem> small, big;
             int64_t vtCursor = 0;
@@ -494,7 +495,7 @@ static int run_plan(vsr_sttn* h, PlanDev* pd, hipStream_t stream)
         // (mode 2 brackets the launches of the NK kernel the convolutions are on, the 128 x 64 tile: the symbol `roofline` is taken on)
         const bool timed = h->timing == 1 || (h->timing == 2 && od.kind == OP_GEMM && od.tileCfg == VSR_TILE_128x64 && od.bmode == VSR_BMODE_NK && !od.thin);
         if (timed) {
-            tr.tag = od.tag; tr.flops = od.flops;
+            tr.tag = od.tag; tr.flops = od.flops; tr.flopsExec = od.flopsExec;
             // an op whose problems all went to the 8-wave kernel is that kernel's launch; one that was cut in two keeps the tile's name + "m"
             const bool big = od.kind == OP_GEMM && od.total7 > 0;
             tr.kernel = od.kind != OP_GEMM ? ("kernel:op:" + std::to_string(od.kind))
@@ -590,7 +591,7 @@ static int collect_timing(vsr_sttn* h, hipStream_t stream)
             auto& acc = h->timed[*key];
             acc.first += ms;
             acc.second.first += 1;
-            acc.second.second += tr.flops;
+            acc.second.second += key == &tr.kernel ? tr.flopsExec : tr.flops;
         }
         (void)hipEventDestroy(tr.a);
         (void)hipEventDestroy(tr.b);
@@ -1177,6 +1178,7 @@ int vsr_switch_state(const char* name)
     if (n == "VSR_DECODE_COLS") return switch_cols_on() ? 1 : 0;
     if (n == "VSR_QKV0_SHARED") return Tuning::get(0).shareQkv0 ? 1 : 0;
     if (n == "VSR_TRIM_LAST_BLOCK") return Tuning::get(0).trimLastBlock ? 1 : 0;
+    if (n == "VSR_SKIP_PAD_TAPS") return Tuning::get(0).skipPadTaps ? 1 : 0;
     return -1;
 }
 
@@ -1505,5 +1507,6 @@ int vsr_plan_counts(const vsr_plan_t* p, int32_t* counts)
     return 0;
 }
 double vsr_plan_flops(const vsr_plan_t* p) { return p ? p->plan->flops : -1.0; }
+double vsr_plan_flops_executed(const vsr_plan_t* p) { return !p ? -1.0 : (p->plan->flopsExecuted >= 0 ? p->plan->flopsExecuted : p->plan->flops); }
 
 } // extern "C"

@@ -1,6 +1,7 @@
 // Plan builder + weight packer for the STTN hot path (see sttn_plan.h).
 #include "sttn_plan.h"
 #include "gather_gemm.h"
+#include <algorithm>
 #include <assert.h>
 #include <math.h>
 #include <stdexcept>
@@ -33,6 +34,7 @@ const Tuning& Tuning::get(int precision)
             x.outConvBlocked = envInt("VSR_OUT_CONV_BLOCKED", 1);
             x.trimLastBlock = envInt("VSR_TRIM_LAST_BLOCK", 1);
             x.shareQkv0 = envInt("VSR_QKV0_SHARED", 0);
+            x.skipPadTaps = envInt("VSR_SKIP_PAD_TAPS", 1);
             return x;
         }(),
         [] {
@@ -47,6 +49,7 @@ const Tuning& Tuning::get(int precision)
             x.outConvBlocked = envInt("VSR_OUT_CONV_BLOCKED", 1);
             x.trimLastBlock = envInt("VSR_TRIM_LAST_BLOCK", 1);
             x.shareQkv0 = envInt("VSR_QKV0_SHARED", 0);
+            x.skipPadTaps = envInt("VSR_SKIP_PAD_TAPS", 1);
             return x;
         }()};
     return t[precision ? 1 : 0];
@@ -370,6 +373,33 @@ int PlanBuilder::tColsConvHW(const Act& a, int kh, int kw, int dil, int c0, int 
     return table(key, std::move(v));
 }
 
+int PlanBuilder::tColsConvTaps(const Act& a, int dil, unsigned taps)
+{
+    const std::string key = "CT:" + std::to_string(a.halo) + ":" + std::to_string(a.W) + ":" + std::to_string(a.C) + ":" +
+                            std::to_string(dil) + ":" + std::to_string(taps);
+    auto it = tableKey_.find(key);
+    if (it != tableKey_.end()) return it->second;
+    if (a.halo < dil) throw std::runtime_error("activation halo too small for conv");
+    if (a.C % VSR_GG_KC) throw std::runtime_error("conv input channels must be a multiple of 32");
+    std::vector<int32_t> v;
+    for (int c = 0; c < a.C; c += VSR_GG_KC)        // mirrors tColsConvHW, channel-major
+        for (int tap = 0; tap < 9; ++tap)
+            if (taps >> tap & 1) v.push_back((int32_t)(((int64_t)(tap / 3 - 1) * dil * a.Wp() + (tap % 3 - 1) * dil) * a.C + c));
+    return table(key, std::move(v));
+}
+
+int PlanBuilder::tColsWeightTaps(int cin, unsigned taps)
+{
+    const std::string key = "CW:" + std::to_string(cin) + ":" + std::to_string(taps);
+    auto it = tableKey_.find(key);
+    if (it != tableKey_.end()) return it->second;
+    std::vector<int32_t> v;
+    for (int c = 0; c < cin; c += VSR_GG_KC)        // mirrors Model::pack_conv, channel-major: chunk (c / 32) * 9 + tap
+        for (int tap = 0; tap < 9; ++tap)
+            if (taps >> tap & 1) v.push_back((c / VSR_GG_KC * 9 + tap) * VSR_GG_KC);
+    return table(key, std::move(v));
+}
+
 int PlanBuilder::tRowsLinear(int count, int ld, int padTo)
 {
     const std::string key = "RL:" + std::to_string(count) + ":" + std::to_string(ld) + ":" + std::to_string(padTo);
@@ -503,35 +533,61 @@ void Plan::addConv(const char* tag, const Act& in, const std::vector<int>& inIds
     op.tileCfg = pickTile(w.cout);
     int BM, BN;
     tileDims(op.tileCfg, BM, BN);
-    GemmItem it{};
-    it.M = nOut * oh * ow;
-    it.N = w.cout;
-    it.K = w.K;
-    it.tilesM = cdiv(it.M, BM);
-    it.tilesN = cdiv(it.N, BN);
-    it.splitK = 1;
-    it.chunksPerSplit = it.K / VSR_GG_KC;
-    it.splitStride = 0;
-    it.alpha = 1.f;
-    it.act = act;
-    it.bufA = in.buf; it.offA = 0;
-    it.tRowA = rect ? tRowsActRect(in, inIds, ylo, yhi, xlo, xhi, BM) : tRowsAct(in, inIds, oh, out.W, stride, BM, (int64_t)ylo * in.Wp() * in.C);
-    it.tColA = tColsConv(in, ksz, dil);
-    it.bufB = BUF_WEIGHTS; it.offB = w.w;
-    it.tRowB = tRowsLinear(it.N, it.K, BN);
-    it.tColB = tColsLinear(it.K / VSR_GG_KC, it.K / VSR_GG_KC);
-    it.bufC = out.buf; it.offC = 0;
-    it.tRowC = rect ? tRowsActRect(out, iota(nOut), ylo, yhi, xlo, xhi, BM) : tRowsAct(out, iota(nOut), oh, out.W, 1, BM, (int64_t)ylo * out.Wp() * out.C);
-    it.tColC = tColsLinear(cdiv(it.N, VSR_GG_KC), it.tilesN * BN / VSR_GG_KC);
-    it.offBias = w.b;
-    if (res) {
-        it.bufR = res->buf; it.offR = 0;
-        it.tRowR = rect ? tRowsActRect(*res, *resIds, ylo, yhi, xlo, xhi, BM) : tRowsAct(*res, *resIds, oh, out.W, 1, BM, (int64_t)ylo * res->Wp() * res->C);
+    // output rows [y0, y1) x the op's columns as one problem over the taps whose bit is set (0x1ff: all nine, the plain tables)
+    auto item = [&](int y0, int y1, unsigned taps) {
+        const int rows = y1 - y0;
+        int ntaps = 0;
+        for (int t = 0; t < ksz * ksz; ++t) ntaps += taps >> t & 1;
+        const bool all = ntaps == ksz * ksz;
+        GemmItem it{};
+        it.M = nOut * rows * ow;
+        it.N = w.cout;
+        it.K = all ? w.K : ntaps * in.C;
+        it.tilesM = cdiv(it.M, BM);
+        it.tilesN = cdiv(it.N, BN);
+        it.splitK = 1;
+        it.chunksPerSplit = it.K / VSR_GG_KC;
+        it.splitStride = 0;
+        it.alpha = 1.f;
+        it.act = act;
+        it.bufA = in.buf; it.offA = 0;
+        it.tRowA = rect ? tRowsActRect(in, inIds, y0, y1, xlo, xhi, BM) : tRowsAct(in, inIds, rows, out.W, stride, BM, (int64_t)y0 * in.Wp() * in.C);
+        it.tColA = all ? tColsConv(in, ksz, dil) : tColsConvTaps(in, dil, taps);
+        it.bufB = BUF_WEIGHTS; it.offB = w.w;
+        it.tRowB = tRowsLinear(it.N, w.K, BN);
+        it.tColB = all ? tColsLinear(it.K / VSR_GG_KC, it.K / VSR_GG_KC) : tColsWeightTaps(in.C, taps);
+        it.bufC = out.buf; it.offC = 0;
+        it.tRowC = rect ? tRowsActRect(out, iota(nOut), y0, y1, xlo, xhi, BM) : tRowsAct(out, iota(nOut), rows, out.W, 1, BM, (int64_t)y0 * out.Wp() * out.C);
+        it.tColC = tColsLinear(cdiv(it.N, VSR_GG_KC), it.tilesN * BN / VSR_GG_KC);
+        it.offBias = w.b;
+        if (res) {
+            it.bufR = res->buf; it.offR = 0;
+            it.tRowR = rect ? tRowsActRect(*res, *resIds, y0, y1, xlo, xhi, BM) : tRowsAct(*res, *resIds, rows, out.W, 1, BM, (int64_t)y0 * res->Wp() * res->C);
+        } else {
+            it.bufR = -1; it.offR = 0; it.tRowR = -1;
+        }
+        op.gemm.push_back(it);
+    };
+    // Tuning::skipPadTaps: the inputs carry a physical zero halo, so for the output rows y < dil the tap row ky = 0 reads nothing but
+    // zeros, and for y >= H - dil the tap row ky = 2 (a third of the conv's products on those rows).  Those rows are problems of their
+    // own in the same launch -- K = 6 * cin: per channel chunk the six taps that are left, in the order of the full problem; B's
+    // chunk table names the same chunks of the unchanged packed weights -- listed largest first so that the short tiles fill the
+    // tail.  A product that is left out would have added +-0 to an accumulator that starts at +0 and can never be -0 (+0 + -0 = +0),
+    // the others keep their order: the same bits.  Columns are left alone (2 of 160: problems of 450 rows for 0.3 % of the step).
+    const int H = out.H;
+    if (tu_.skipPadTaps && tu_.convChannelMajor && ksz == 3 && stride == 1 && in.H == H && H >= 2 * dil) {
+        const int topHi = yhi < dil ? yhi : dil, botLo = ylo > H - dil ? ylo : H - dil;      // [ylo, topHi) and [botLo, yhi): the border rows
+        const int midLo = ylo > dil ? ylo : dil, midHi = yhi < H - dil ? yhi : H - dil;
+        if (midHi > midLo) item(midLo, midHi, 0x1ff);
+        if (topHi > ylo) item(ylo, topHi, 0x1f8);         // ky >= 1
+        if (yhi > botLo) item(botLo, yhi, 0x03f);         // ky <= 1
+        std::stable_sort(op.gemm.begin(), op.gemm.end(), [](const GemmItem& a, const GemmItem& b) { return (int64_t)a.M * a.K > (int64_t)b.M * b.K; });
     } else {
-        it.bufR = -1; it.offR = 0; it.tRowR = -1;
+        item(ylo, yhi, (1u << (ksz * ksz)) - 1);
     }
-    op.flops = 2.0 * it.M * it.N * (double)(ksz * ksz * in.C);
-    op.gemm.push_back(it);
+    op.flops = 2.0 * nOut * oh * ow * (double)w.cout * (double)(ksz * ksz * in.C);
+    op.flopsExecuted = 0;
+    for (const GemmItem& it : op.gemm) op.flopsExecuted += 2.0 * it.M * (double)it.N * it.K;
     need(out.buf, (int64_t)nOut * out.frameElems());
     flops += op.flops;
     ops.push_back(std::move(op));
@@ -1074,6 +1130,8 @@ Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, i
     lane_ = 0;
     compCount = visits;
     refFlops = flops + trimmedFlops_;
+    flopsExecuted = 0;
+    for (const Op& op : ops) flopsExecuted += op.flopsExecuted >= 0 ? op.flopsExecuted : op.flops;
     // (the reference runs the whole list: what it spends is the plain plan's count, dropped windows and context decodes included)
     if (nCtx > 0) refFlops = Plan(model, L_, precision_, 1, decLo_, decHi_, decXLo_, decXHi_).refFlops;
 }

@@ -42,6 +42,8 @@ struct Tuning {
                          //   FFN for the NEIGHBOUR frames only -- the decoder reads nothing else (Plan::buildWindow); same bits
     int fuseSoftmax;     // VSR_FUSE_SOFTMAX: 1 = exact-fp32 mode keeps no probability matrix for the scales whose scores are not
                          //   split along K: row max in the QK^T epilogue, exp + row sum while P.V stages its A tiles (0 = k_softmax_rows)
+    int skipPadTaps;     // VSR_SKIP_PAD_TAPS: 1 = a stride-1 3x3 conv contracts the rows next to the top / bottom border in problems of their
+                         //   own, without the tap row that lies wholly in the zero halo (Plan::addConv); same bits, 2-4 % fewer products per conv
     // precision 0: exact fp32 MFMA kernels; 1: split-half f16 MFMA kernels (larger tiles pay there)
     static const Tuning& get(int precision = 0);
 };
@@ -140,6 +142,7 @@ struct Op {
     int M = 0, N = 0, nsplit = 0, tRowC = -1, tColC = -1;
     int64_t offSrc = 0, offDst = 0, splitStride = 0;
     double flops = 0;                    // algorithmic flops of this op (2*M*N*K, unpadded)
+    double flopsExecuted = -1;           // what the op's problems contract where that is less (Tuning::skipPadTaps); -1 = `flops`
     int lane = 0;                        // STTN: the stream this op is issued on (0 = the caller's; ops in list order are a valid serial schedule)
     std::string tag;
     // OP_EW: sub-kind + generic operands (buffers, element offsets, integer / float parameters; meaning per sub-kind)
@@ -171,6 +174,7 @@ struct PlanIR {
     std::vector<Op> ops;
     std::vector<int32_t> compCount;       // STTN: decodes per frame (1 => comp stays u8)
     double flops = 0;                     // algorithmic model flops of the whole call (what the plan's GEMMs contract)
+    double flopsExecuted = -1;            // STTN: `flops` without the products a conv's border problems leave out (Op::flopsExecuted); -1 = `flops`
     double refFlops = 0;                  // STTN: flops of the call as the reference computes it -- `flops` + the rows of the last block
                                           // that nothing reads (Plan::buildWindow); equal to `flops` for every other plan
     virtual ~PlanIR() {}
@@ -188,6 +192,10 @@ protected:
     // 32-channel chunk offsets of a kh x kw window (dilation dil) over channels [c0, c0+cin) of `a`; K order mirrors pack
     int tColsConvHW(const Act& a, int kh, int kw, int dil, int c0 = 0, int cin = -1);
     int tColsConv(const Act& a, int ksz, int dil) { return tColsConvHW(a, ksz, ksz, dil); }
+    // the taps of a 3x3 window whose bit (ky * 3 + kx) is set in `taps`, channel-major K order: the chunks of tColsConv(a, 3, dil) that
+    // are kept, in its order -- and where the same chunks of the packed weights [cout][9 * cin] start (B's chunk table)
+    int tColsConvTaps(const Act& a, int dil, unsigned taps);
+    int tColsWeightTaps(int cin, unsigned taps);
     int tRowsLinear(int count, int ld, int padTo);
     int tColsLinear(int nchunks, int padTo);
     void need(int buf, int64_t elems);

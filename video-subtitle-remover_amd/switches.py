@@ -12,10 +12,14 @@ of the same name ("0" / "1") overrides.
     VSR_QKV0_SHARED     STTN: the first transformer block's q/k/v once per frame of a chunk instead of once per window (csrc/sttn_plan.cpp;
                         read by the library itself, once per process: _lib.py exports the default into the environment before it loads)
                         -- default ON since round 5: 216.3 -> 217.6 fps on the headline, same bits
+    VSR_SKIP_PAD_TAPS   STTN: the rows of a stride-1 3x3 conv next to the top / bottom border as problems of their own, without the tap row that
+                        reads only the zero halo (csrc/sttn_plan.cpp Plan::addConv; read by the library itself, once per process)
+                        -- default ON: 219.6 -> 222.6 fps on the headline (parent and this build interleaved, four runs each,
+                        profiles/r07_pad_taps_ab.log), same bits (tests/test_pad_taps.py, tests/test_gpu_pad_taps.py)
 """
 import os
 
-DEFAULTS = {"VSR_DECODE_COLS": "1", "VSR_PP_DECODE_BOX": "1", "VSR_PP_ENC_CACHE": "1", "VSR_QKV0_SHARED": "1"}
+DEFAULTS = {"VSR_DECODE_COLS": "1", "VSR_PP_DECODE_BOX": "1", "VSR_PP_ENC_CACHE": "1", "VSR_QKV0_SHARED": "1", "VSR_SKIP_PAD_TAPS": "1"}
 
 
 def export_defaults():
@@ -24,7 +28,7 @@ def export_defaults():
         os.environ.setdefault(k, v)
 
 
-LIBRARY_SIDE = ("VSR_DECODE_COLS", "VSR_QKV0_SHARED")      # switches libvsr_hip.so reads itself, once per process
+LIBRARY_SIDE = ("VSR_DECODE_COLS", "VSR_QKV0_SHARED", "VSR_SKIP_PAD_TAPS")      # switches libvsr_hip.so reads itself, once per process
 
 
 def on(name):
