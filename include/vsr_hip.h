@@ -105,6 +105,18 @@ int vsr_sttn_auto_chunk_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, in
                             const int32_t* sel, int nsel, const uint8_t* ctx_dev, int n_ctx, void* stream);
 /* FLOPs of that call's plan: a list of L frames (context included) whose first n_ctx are context, decoder box as vsr_sttn_flops_box */
 double vsr_sttn_flops_ctx(vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi);
+/* ... and with look-ahead context as well (sttn-det: vsr_sttn_det_batch_ctx2): after_dev uint8 [n_after][H][W][3], frames of the same geometry that
+ * come BEHIND the L of frames_dev in the video.  The result written into frames_dev is what vsr_sttn_auto_chunk_box writes at positions
+ * [n_ctx, n_ctx + L) (the selected ones) of the list ctx ++ frames ++ after, bit for bit.  Both context pointers are only read; the
+ * last block's query rows, the decoder, the running average and the resize back run for the written neighbours of a window -- one
+ * contiguous run of them -- and a window all of whose neighbours are context, at either end, is not run (Plan::nCtx, Plan::nAfter).
+ * n_after = 0 (after_dev ignored) is vsr_sttn_auto_chunk_ctx.  At most 127 context frames on each side. */
+int vsr_sttn_auto_chunk_ctx2(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev,
+                             int n_areas, const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols,
+                             const int32_t* sel, int nsel, const uint8_t* ctx_dev, int n_ctx, const uint8_t* after_dev, int n_after,
+                             void* stream);
+/* FLOPs of that call's plan: a list of L frames (context included) whose first n_ctx and last n_after are context */
+double vsr_sttn_flops_ctx2(vsr_sttn_t* h, int L, int n_ctx, int n_after, int row_lo, int row_hi, int col_lo, int col_hi);
 /* the column half of the same two questions (what VSR_DECODE_COLS=1 makes vsr_sttn_auto_chunk_box / vsr_sttn_det_batch_box do): the model columns
  * [*col_lo, *col_hi) decoded for a mask in frame columns [mask_col_lo, mask_col_hi) of a frame_w-wide frame (0, 0: all), and the
  * FLOPs of a plan restricted to a box of model rows and columns */
@@ -145,6 +157,13 @@ int vsr_sttn_det_batch_rows(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, in
 int vsr_sttn_det_batch_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
                            const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const uint8_t* ctx_dev, int n_ctx,
                            void* stream);
+/* ... and with look-ahead context: after_dev uint8 [n_after][H][W][3], frames that come BEHIND the L of frames_dev.  The result is what
+ * vsr_sttn_det_batch_box writes at positions [n_ctx, n_ctx + L) of the list ctx ++ frames ++ after, bit for bit; every frame of the
+ * list gets the same mask strip, both context pointers are only read (Plan::nAfter).  n_after = 0 is vsr_sttn_det_batch_ctx.  At
+ * most 127 context frames on each side.  vsr_sttn_flops_ctx2 and vsr_plan_create_ctx2 on a det handle give this call's plan. */
+int vsr_sttn_det_batch_ctx2(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
+                            const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const uint8_t* ctx_dev, int n_ctx,
+                            const uint8_t* after_dev, int n_after, void* stream);
 
 /* Arithmetic of the contractions.  0 (default): exact fp32 -- v_mfma_f32_32x32x2_f32, bitwise an fmaf chain.
  * 1: split-half -- fp32 data and fp32 accumulation, each fp32 operand fed to the f16 matrix cores as
@@ -690,6 +709,8 @@ int vsr_plan_create_rows(const vsr_sttn_t* h, int L, int row_lo, int row_hi, vsr
 int vsr_plan_create_box(const vsr_sttn_t* h, int L, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);   /* ... and columns */
 /* ... of L frames whose first n_ctx are read-only context (vsr_sttn_auto_chunk_ctx, vsr_sttn_det_batch_ctx); works on a host-only handle like the others */
 int vsr_plan_create_ctx(const vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);
+/* ... and whose last n_after are read-only context too (the _ctx2 entry points); n_after = 0 is vsr_plan_create_ctx op for op */
+int vsr_plan_create_ctx2(const vsr_sttn_t* h, int L, int n_ctx, int n_after, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);
 int vsr_raft_plan_create(const vsr_raft_t* h, int t, int H, int W, int iters, vsr_plan_t** out);
 int vsr_rfc_plan_create(const vsr_rfc_t* h, int t, int H, int W, vsr_plan_t** out);
 int vsr_pp_imgprop_plan_create(int t, int H, int W, vsr_plan_t** out);

@@ -88,6 +88,8 @@ SIGNATURES = {
     "vsr_sttn_auto_chunk_box": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
     "vsr_sttn_auto_chunk_ctx": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P]),
     "vsr_sttn_flops_ctx": (_D, [_P, _I, _I, _I, _I, _I, _I]),
+    "vsr_sttn_auto_chunk_ctx2": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P]),
+    "vsr_sttn_flops_ctx2": (_D, [_P, _I, _I, _I, _I, _I, _I, _I]),
     "vsr_sttn_det_batch_box": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     "vsr_sttn_decode_rows": (_I, [_P, _I, _I, _I, _P, _P]),
     "vsr_sttn_decode_cols": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -97,6 +99,7 @@ SIGNATURES = {
     "vsr_sttn_det_batch": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "vsr_sttn_det_batch_rows": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P]),
     "vsr_sttn_det_batch_ctx": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "vsr_sttn_det_batch_ctx2": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P]),
     "vsr_sttn_set_precision": (_I, [_P, _I]),
     "vsr_sttn_set_lanes": (_I, [_P, _I]),
     "vsr_sttn_fallbacks": (_L, [_P]),
@@ -121,6 +124,7 @@ SIGNATURES = {
     "vsr_plan_create_rows": (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
     "vsr_plan_create_box": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "vsr_plan_create_ctx": (_I, [_P, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
+    "vsr_plan_create_ctx2": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "vsr_raft_plan_create": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P)]),
     "vsr_raft_create": (_I, [C.POINTER(_P)]),
     "vsr_raft_set_param": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _I]),

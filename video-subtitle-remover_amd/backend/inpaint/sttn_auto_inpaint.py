@@ -6,7 +6,8 @@ Mirrors backend/inpaint/sttn_auto_inpaint.py:
       inpaint(frames) -> comp frames                      :122-164
       get_ref_index(neighbor_ids, length)                 :107-120
   STTNAutoInpaint(device, model_path, video_path, mask_path=None, clip_gap=None)   :182-197
-      (+ context=None, scene_split=None: look-back context frames and scene-bounded chunks, not in the reference -- _run)
+      (+ context=None, scene_split=None, lookahead=None: look-back / look-ahead context frames and scene-bounded chunks, not in the
+       reference -- _run)
       __call__(input_mask=None, input_sub_remover=None, tbar=None)                 :199-336
 
 Arithmetic happens in libvsr_hip.so (there is no torch model and no CPU path here); this file
@@ -124,9 +125,10 @@ class _ResidentFrames:
 
 
 class STTNAutoInpaint:
-    def __init__(self, device, model_path, video_path, mask_path=None, clip_gap=None, context=None, scene_split=None):
+    def __init__(self, device, model_path, video_path, mask_path=None, clip_gap=None, context=None, scene_split=None, lookahead=None):
         self.sttn_inpaint = STTNInpaint(device, model_path)
         self.context, self.scene_split = context, scene_split    # None: VSR_STTN_CONTEXT / VSR_SCENE_SPLIT (tools/chunk_parallel.lookback_options)
+        self.lookahead = lookahead                               # None: VSR_STTN_LOOKAHEAD (the same function)
         self.video_path = video_path
         self.mask_path = mask_path
         if isinstance(video_path, (str, os.PathLike)):
@@ -158,14 +160,20 @@ class STTNAutoInpaint:
         restarts at every cut (cp.scene_chunk_ranges): no chunk feeds frames of another scene to the attention.  context = N: a chunk
         that continues a scene also sees the N SOURCE frames in front of it (never an inpainted result, never across a cut): the
         strip rows of a chunk's last N frames are copied aside on the device before it is inpainted and handed to the next chunk's
-        engine call (SttnEngine.auto_chunk(context=...)), which reads them and writes the chunk alone.  One process only."""
+        engine call (SttnEngine.auto_chunk(context=...)), which reads them and writes the chunk alone.  One process only.
+        lookahead = M: the mirror image -- a chunk also sees the first M SOURCE frames of the chunk behind it, unless that one starts a
+        scene.  The next chunk is already staged on the device when this one is computed and is inpainted only afterwards, so the
+        chunk loop hands its first rows over as a read-only view (cp.run_chunk_parallel(lookahead=M)): no copy.  A short read of the
+        next chunk gives what was read of it."""
         from ..tools import chunk_parallel as cp
 
-        n_context, scene_split = cp.lookback_options(self.context, self.scene_split, self.clip_gap)      # bad values: before any frame is read
+        n_context, scene_split, n_ahead = cp.lookback_options(self.context, self.scene_split, self.clip_gap,
+                                                              lookahead=self.lookahead)                  # bad values: before any frame is read
         feather = seam_feather.refuse_ranks(dist)            # --seam-feather: one process (bad values and several ranks: before any frame is read)
-        if (n_context or scene_split) and dist is not None:
-            raise RuntimeError("sttn-auto context frames / scene-bounded chunks run in one process: a chunk looks back at its predecessor's "
-                               f"frames, which another rank holds (world size {dist.get_world_size()}); run without them or on one GPU")
+        if (n_context or scene_split or n_ahead) and dist is not None:
+            raise RuntimeError("sttn-auto context frames (--sttn-context, --sttn-lookahead) / scene-bounded chunks run in one process: a chunk looks "
+                               "back at its predecessor's frames and ahead at its successor's, "
+                               f"which another rank holds (world size {dist.get_world_size()}); run without them or on one GPU")
         rank = dist.get_rank() if dist is not None else 0
         engine = self.sttn_inpaint.engine
         cuts = []
@@ -223,9 +231,14 @@ class STTNAutoInpaint:
                 print(f"Warning: No valid frames found in range {s + 1}-{e}. Skipping this segment.")
             kept[i] = frames
 
-        def process(i, rows):
+        def process(i, rows, nxt=None):
             s, e = ranges[i]
             n = len(kept[i]) if i in kept else e - s     # the owner of the frame source knows how many frames were read
+            ahead = None
+            if nxt is not None and ranges[i + 1][0] not in scene_starts:
+                # look-ahead: the first source rows of the chunk behind (what was read of it) unless that one starts a scene
+                k = min(n_ahead, len(kept[i + 1]) if i + 1 in kept else nxt.shape[0])
+                ahead = nxt[:k] if k else None
             context = None
             if n_context:
                 # look-back: the last source rows of the chunk before (what was read of it) unless this one starts a scene; this
@@ -241,7 +254,7 @@ class STTNAutoInpaint:
             sel = [j - s for j in range(s, s + n) if is_frame_number_in_ab_sections(j, ab_sections)]
             if sel:
                 self.sttn_inpaint.auto_chunk(rows[:n], dmask, local_areas, cmask=cmask, rows=(y_lo, y_hi), sel=None if len(sel) == n else sel,
-                                             mask_host=mask_rows_host, context=context)
+                                             mask_host=mask_rows_host, context=context, **({} if ahead is None else {"lookahead": ahead}))
 
         def store(i, rows):
             for j, frame in enumerate(kept.pop(i)):
@@ -251,7 +264,7 @@ class STTNAutoInpaint:
                 tick(original, frame)
 
         # (the by-offset path deals whole chunks to workers with no order between them: with a look-back the funnel path is taken)
-        local = None if (n_context or scene_split) else self._rank_local_io(dist, rank, reader, writer, gui, inpaint_area, frame_info["len"])
+        local = None if (n_context or scene_split or n_ahead) else self._rank_local_io(dist, rank, reader, writer, gui, inpaint_area, frame_info["len"])
         if local is not None:
             # every rank reads and writes its own chunks by offset (tools/rank_io.py): no rank-0 funnel, no collective on the data path
             try:
@@ -278,7 +291,7 @@ class STTNAutoInpaint:
             else:
                 # `io` only changes what rank 0 hands to load / store (pinned host rows or device rows); the exchange is the same
                 cp.run_chunk_parallel(ranges, (y_hi - y_lo, W_ori, 3), load, process, store, dist=dist, device=engine.device,
-                                      io="device" if resident is not None else "host")
+                                      io="device" if resident is not None else "host", **({"lookahead": n_ahead} if n_ahead else {}))
         finally:
             getattr(store, "close", lambda: None)()      # the resident path's page-locking thread (tools/pinned.py)
             reader.release()

@@ -431,28 +431,30 @@ class SubtitleRemover:
         Two options that are not the reference's, both off by default (then every job, every plugin call and every byte are what
         they were) and read only for a plugin that takes context frames (sttn-det; lama and opencv ignore them): --scene-split cuts
         every interval at the scene starts, --sttn-context N lets every batch look back at the N source frames in front of it inside
-        its piece (tools/det_lookback.py holds the definition).  One process, no resident windows."""
+        its piece, --sttn-lookahead M at the M source frames behind it inside its piece (tools/det_lookback.py holds the definition).
+        One process, no resident windows."""
         from .tools import det_lookback
 
         from .tools import seam_feather
 
         seam_feather.refuse_ranks(self._distributed())                                  # --seam-feather: bad values and several ranks, before any frame is read
         max_load = config.getSttnMaxLoadNum()
-        n_context, scene_split = (0, False)
+        n_context, scene_split, n_ahead = (0, False, 0)
         if getattr(model, "accepts_context", False):
-            n_context, scene_split = det_lookback.lookback_options(max_load)           # bad values: before any frame is read
-        lookback = bool(n_context or scene_split)
+            n_context, scene_split, n_ahead = det_lookback.lookback_options(max_load, lookahead=None)   # bad values: before any frame is read
+        lookback = bool(n_context or scene_split or n_ahead)
         dist = self._distributed()
         if lookback and dist is not None:
-            raise RuntimeError("sttn-det context frames / scene-bounded intervals run in one process: a batch looks back at its predecessor's "
-                               f"frames, which another rank holds (world size {dist.get_world_size()}); run without them or on one GPU")
+            raise RuntimeError("sttn-det context frames (--sttn-context, --sttn-lookahead) / scene-bounded intervals run in one process: a batch "
+                               "looks back at its predecessor's frames and ahead at its successor's, "
+                               f"which another rank holds (world size {dist.get_world_size()}); run without them or on one GPU")
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), model)
         on_device = getattr(model, "accepts_device_frames", False)
         wclip = self._open_windowed() if lookback and on_device else None      # (the header only: no frame is read)
         if wclip is not None:
-            raise RuntimeError("sttn-det context frames / scene-bounded intervals do not run in resident windows (--resident-windows on a clip "
-                               "over VSR_RESIDENT_GB): a batch looks back across window boundaries; run without them, without "
+            raise RuntimeError("sttn-det context frames (--sttn-context, --sttn-lookahead) / scene-bounded intervals do not run in resident windows "
+                               "(--resident-windows on a clip over VSR_RESIDENT_GB): a batch looks back and ahead across window boundaries; run without them, without "
                                "--resident-windows, or with a larger VSR_RESIDENT_GB")
         detector = SubtitleDetect(self.video_path, self.sub_areas, text_detector=text_detector)
         resident = self._open_resident() if on_device else None
@@ -515,9 +517,10 @@ class SubtitleRemover:
             def inpaint_all():
                 if lookback:
                     # (the source rows a later batch looks back at are copied aside before their batch is inpainted: ResidentLookback)
-                    jobs = det_lookback.det_jobs(start_end, len(clip), interval_mask, cuts, n_context, max_load)
-                    self._run_resident_jobs([(clip.frames[lo:hi], mask) for lo, hi, _, mask in jobs], model, clip, store,
-                                            det_lookback.ResidentLookback(clip.frames, jobs) if n_context else None)
+                    # (... and the rows a batch looks ahead at, by that batch, before their owners are)
+                    jobs = det_lookback.det_jobs(start_end, len(clip), interval_mask, cuts, n_context, max_load, n_ahead if n_ahead else None)
+                    self._run_resident_jobs([(clip.frames[job[0]:job[1]], job[3]) for job in jobs], model, clip, store,
+                                            det_lookback.ResidentLookback(clip.frames, jobs) if (n_context or n_ahead) else None)
                     return
                 jobs = [(clip.frames[lo:hi], mask) for lo, hi, mask in index_jobs(len(clip))]
                 self._run_resident_jobs(jobs, model, clip, store)
@@ -534,17 +537,20 @@ class SubtitleRemover:
             return
         reader = open_video(self.video_path)
         process = model
-        if n_context:
-            # host frames: a batch's context goes along with its work item, in front of the batch's frames (they are still the source's
-            # here); how many of an item's frames are context waits in a queue that items() fills and the plugin call empties, both in
+        if n_context or n_ahead:
+            # host frames: a batch's context goes along with its work item, in front of the batch's frames and behind them (they are still
+            # the source's here: an interval is read whole before its batches are made); how many of an item's leading and trailing frames
+            # are context waits in a queue that items() fills and the plugin call empties, both in
             # item order (one process: tools/batch_parallel.py hands the items to `process` one by one, as they come)
             import collections
 
             n_ctx_of = collections.deque()
 
             def process(frames, mask):
-                k = n_ctx_of.popleft()
-                return model(frames[k:], mask, context=frames[:k])
+                k, ka = n_ctx_of.popleft()
+                if not ka:
+                    return model(frames[k:], mask, context=frames[:k])
+                return model(frames[k:len(frames) - ka], mask, context=frames[:k], lookahead=frames[len(frames) - ka:])
 
         def items():
             idx = 0
@@ -566,10 +572,10 @@ class SubtitleRemover:
                     frames.append(frame)
                 mask = interval_mask(first, last)
                 if lookback:
-                    for lo, hi, ctx_lo in det_lookback.piece_jobs(first - 1, first - 1 + len(frames), cuts, n_context, max_load):
-                        if n_context:
-                            n_ctx_of.append(lo - ctx_lo)
-                        yield ("work", frames[ctx_lo - (first - 1):hi - (first - 1)], mask)
+                    for lo, hi, ctx_lo, ahead_hi in det_lookback.piece_jobs(first - 1, first - 1 + len(frames), cuts, n_context, max_load, n_ahead):
+                        if n_context or n_ahead:
+                            n_ctx_of.append((lo - ctx_lo, ahead_hi - hi))
+                        yield ("work", frames[ctx_lo - (first - 1):ahead_hi - (first - 1)], mask)
                     continue
                 for batch in batch_generator(frames, config.getSttnMaxLoadNum()):
                     if len(batch) >= 1:
@@ -577,7 +583,7 @@ class SubtitleRemover:
 
         try:
             self._timed("read + inpainting + write (host frames)", self._run_items, tbar, items(), process)
-            if n_context and n_ctx_of:
+            if (n_context or n_ahead) and n_ctx_of:
                 raise RuntimeError(f"sttn-det look-back: {len(n_ctx_of)} work items were made and never inpainted")
         finally:
             reader.release()
@@ -708,6 +714,8 @@ def main(argv=None):
         os.environ["VSR_SCENE_SPLIT"] = "1"
     if args.sttn_context is not None:
         os.environ["VSR_STTN_CONTEXT"] = str(args.sttn_context)
+    if args.sttn_lookahead is not None:
+        os.environ["VSR_STTN_LOOKAHEAD"] = str(args.sttn_lookahead)
     if args.seam_feather is not None:
         os.environ["VSR_SEAM_FEATHER"] = str(args.seam_feather)
     sr = SubtitleRemover(args.input)

@@ -31,6 +31,10 @@ def build_parser():
                         help="sttn-auto, sttn-det: every chunk / batch also sees the N source frames in front of it (0 <= N <= the chunk "
                              "length / the batch limit; never across a scene cut with --scene-split, sttn-det: never in front of its "
                              "subtitle interval); sets VSR_STTN_CONTEXT")
+    parser.add_argument("--sttn-lookahead", type=int, default=None, metavar="M",
+                        help="sttn-auto, sttn-det: every chunk / batch also sees the M source frames behind it (0 <= M <= the chunk "
+                             "length / the batch limit; never across a scene cut with --scene-split, sttn-det: never behind its "
+                             "subtitle interval); combines with --sttn-context; sets VSR_STTN_LOOKAHEAD")
     # not in the reference: every mode ends its plugin call with a mask-exact, feathered composite (tools/seam_feather.py)
     parser.add_argument("--seam-feather", type=int, default=None, metavar="F",
                         help="every mode: outside the pixels a plugin blends under, the written frame is the source bit for bit; inside, "

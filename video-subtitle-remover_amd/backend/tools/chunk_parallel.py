@@ -61,26 +61,44 @@ def context_span(piece_start, scene_start, n_context):
     return max(piece_start - int(n_context), scene_start), piece_start
 
 
-def lookback_options(context, scene_split, clip_gap, env=None, what="sttn-auto", bound="clip_gap"):
+def lookahead_span(piece_end, scene_end, n_lookahead):
+    """(lo, hi): the source frames a piece ending at `piece_end` looks ahead at -- the n_lookahead behind it, never across the end of
+    its scene (nor past the last frame, the last scene's end): the mirror image of context_span"""
+    return piece_end, min(piece_end + int(n_lookahead), scene_end)
+
+
+_NO_LOOKAHEAD = object()
+
+
+def lookback_options(context, scene_split, clip_gap, env=None, what="sttn-auto", bound="clip_gap", lookahead=_NO_LOOKAHEAD):
     """(n_context, scene_split) of an sttn-auto run: the constructor's arguments, None = the environment (VSR_STTN_CONTEXT, an
     integer; VSR_SCENE_SPLIT=1).  Off by default.  ValueError for a context that is no integer in [0, clip_gap].
-    (what / bound: the words of the error message -- sttn-det reads the same two variables, tools/det_lookback.lookback_options.)"""
+    (what / bound: the words of the error message -- sttn-det reads the same two variables, tools/det_lookback.lookback_options.)
+    lookahead= (a value, or None = VSR_STTN_LOOKAHEAD): the look-ahead count is read and checked the same way, against the same
+    bound, and the result is (n_context, scene_split, n_lookahead)."""
     import os
 
     env = os.environ if env is None else env
     if scene_split is None:
         scene_split = env.get("VSR_SCENE_SPLIT", "0") == "1"
-    if context is None:
-        context = env.get("VSR_STTN_CONTEXT", "0") or "0"
-    try:
-        n = int(context)
-        if isinstance(context, float) and n != context:
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError(f"{what} context: {context!r} is not an integer") from None
-    if n < 0 or n > int(clip_gap):
-        raise ValueError(f"{what} context: {n} frames asked for, 0 <= N <= {bound} = {int(clip_gap)} are possible")
-    return n, bool(scene_split)
+
+    def count(value, var, word, letter):
+        if value is None:
+            value = env.get(var, "0") or "0"
+        try:
+            n = int(value)
+            if isinstance(value, float) and n != value:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} {word}: {value!r} is not an integer") from None
+        if n < 0 or n > int(clip_gap):
+            raise ValueError(f"{what} {word}: {n} frames asked for, 0 <= {letter} <= {bound} = {int(clip_gap)} are possible")
+        return n
+
+    n = count(context, "VSR_STTN_CONTEXT", "context", "N")
+    if lookahead is _NO_LOOKAHEAD:
+        return n, bool(scene_split)
+    return n, bool(scene_split), count(lookahead, "VSR_STTN_LOOKAHEAD", "look-ahead context", "M")
 
 
 def owner_of(chunk_index, world_size):
@@ -153,7 +171,7 @@ def ring_bytes(maxn, row_shape, world, rank):
     return RING * (world if rank == 0 else 1) * maxn * h * W * C
 
 
-def run_chunk_parallel(ranges, row_shape, load, process, store, dist=None, device="cpu", io="host", workspace_bytes=0):
+def run_chunk_parallel(ranges, row_shape, load, process, store, dist=None, device="cpu", io="host", workspace_bytes=0, lookahead=0):
     """Drive the chunks `ranges` = [(start, end)] of one video over the ranks of `dist` (None = single process).
 
     row_shape = (h, W, C): the rows of a frame that travel.
@@ -163,12 +181,19 @@ def run_chunk_parallel(ranges, row_shape, load, process, store, dist=None, devic
                       its kernels are still running on the current stream.
     store(i, arr)     rank 0 only, in chunk order: the processed rows (same kind of array as load's).
     workspace_bytes   what `process` needs besides the ring (the engine's buffers, if not allocated yet): part of the memory check.
+    lookahead         M > 0 (one process only): process is called as process(i, t, nxt), nxt = a READ-ONLY view of the first min(M, frames of
+                      chunk i + 1) rows of the next chunk's buffer as load left them -- that chunk is staged before chunk i is computed
+                      and is inpainted in place only by the next `process`, on the same compute stream -- or None behind the last
+                      chunk.  0: the calls of old.
 
     A callback that raises does not break the lock step (module docstring): all ranks finish the rounds, then all raise.
     """
     world = dist.get_world_size() if dist is not None else 1
     rank = dist.get_rank() if dist is not None else 0
     h, W, C = row_shape
+    lookahead = int(lookahead)
+    if lookahead > 0 and world > 1:
+        raise RuntimeError(f"look-ahead rows of the next chunk: one process only (world size {world}): another rank holds that chunk")
     n_rounds = (len(ranges) + world - 1) // world
     maxn = max((e - s for s, e in ranges), default=0)
     st = _Streams(device)
@@ -275,6 +300,17 @@ def run_chunk_parallel(ranges, row_shape, load, process, store, dist=None, devic
         if i is None:
             return
         st.wait("cmp", staged.get(r))
+        if lookahead > 0:
+            # (one process: chunk i + 1 is round r + 1, staged by stage(r + 1) before this call; its rows are the source's until
+            # compute(r + 1), which the compute stream runs behind this chunk)
+            nxt = None
+            if i + 1 < len(ranges):
+                st.wait("cmp", staged.get(r + 1))
+                nxt = dbuf[((r + 1) % RING, rank)][:min(lookahead, nframes(i + 1))]
+            with st.on("cmp"):
+                guarded(process, i, dbuf[(r % RING, rank)][:nframes(i)], nxt)
+            computed[r] = st.event("cmp")
+            return
         with st.on("cmp"):
             guarded(process, i, dbuf[(r % RING, rank)][:nframes(i)])
         computed[r] = st.event("cmp")

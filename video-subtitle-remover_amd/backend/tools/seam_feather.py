@@ -142,11 +142,14 @@ def device_call(frames, cmask, body, feather, rows=None):
     return frames if out is None else out
 
 
-def plugin_call(plugin, body, input_frames, input_mask, device, context=None):
-    """The __call__ of a plugin under the option: body(input_frames, input_mask[, context=]) is the plugin's call as it has always
-    been (a list of HxWx3 arrays -> fresh arrays; a uint8 [n,H,W,3] device tensor -> inpainted in place and returned).
-    plugin.composite_mask(input_mask) names the pixels it blends under; device: where the list form uploads to."""
+def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lookahead=None):
+    """The __call__ of a plugin under the option: body(input_frames, input_mask[, context=][, lookahead=]) is the plugin's call as it
+    has always been (a list of HxWx3 arrays -> fresh arrays; a uint8 [n,H,W,3] device tensor -> inpainted in place and returned).
+    plugin.composite_mask(input_mask) names the pixels it blends under; device: where the list form uploads to.  Context frames
+    of either kind (in front of the batch, behind it) are handed through and take no part in the composite."""
     kw = {} if context is None else {"context": context}
+    if lookahead is not None:
+        kw["lookahead"] = lookahead
     f = feather_option()
     if not f:
         return body(input_frames, input_mask, **kw)
@@ -167,8 +170,8 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None):
         composite(frames, src, alpha(cm, f, frames.device), f)
     else:
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
-        if context is not None and len(context):
-            kw = {"context": torch.from_numpy(np.ascontiguousarray(np.stack(context))).to(device)}
+        kw = {name: torch.from_numpy(np.ascontiguousarray(np.stack(c))).to(device)
+              for name, c in (("context", context), ("lookahead", lookahead)) if c is not None and len(c)}
         device_call(frames, cm, lambda t: body(t, input_mask, **kw), f)
     out = frames.cpu().numpy()
     return [out[i] for i in range(out.shape[0])]

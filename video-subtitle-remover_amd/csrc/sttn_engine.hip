@@ -124,7 +124,8 @@ struct vsr_sttn {
     bool finalized = false;
     void* bufs[BUF_COUNT] = {};
     int64_t cap[BUF_COUNT] = {};
-    std::map<int64_t, std::unique_ptr<PlanDev>> plans;
+    // key: (the packed word of build_plan_dev, the look-ahead count) -- the word has no room for a second 7-bit field
+    std::map<std::pair<int64_t, int>, std::unique_ptr<PlanDev>> plans;
     uint64_t useClock = 0;
     std::map<std::pair<int, int>, StripTables> strips;
     float* compAreas = nullptr;
@@ -172,15 +173,18 @@ static int gg_wide_queues()
 
 
 // decLo / decHi: the rows of the model-resolution output the caller will read (Plan::decLo; 0, 0 = all)
-// nCtx: the first nCtx of the L frames are read-only context (Plan::nCtx)
-static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0, int nCtx = 0)
+// nCtx: the first nCtx of the L frames are read-only context (Plan::nCtx); nAfter: so are the last nAfter (Plan::nAfter)
+static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0, int nCtx = 0,
+                          int nAfter = 0)
 {
     // the key packs the four decoder bounds into 10 bits each
     if (h->model.g.modelH >= 1024 || h->model.g.modelW >= 1024 || decLo < 0 || decHi >= 1024 || decXLo < 0 || decXHi >= 1024)
         return fail(VSR_ERR_ARG, "plan key: model resolution / decoder bounds beyond 1023");
     // (L sits above bit 45; the context count takes the seven bits from 56 up, 0 = the key of old)
     if (nCtx < 0 || nCtx >= 128 || (nCtx > 0 && L >= 2048)) return fail(VSR_ERR_ARG, "plan key: at most 127 context frames, in a list of at most 2047");
-    const int64_t key = (((((((int64_t)L * 4 + precision) * 8 + h->lanes) * 1024 + decLo) * 1024 + decHi) * 1024 + decXLo) * 1024 + decXHi) + ((int64_t)nCtx << 56);
+    if (nAfter < 0 || nAfter >= 128) return fail(VSR_ERR_ARG, "plan key: at most 127 look-ahead context frames");
+    const int64_t word = (((((((int64_t)L * 4 + precision) * 8 + h->lanes) * 1024 + decLo) * 1024 + decHi) * 1024 + decXLo) * 1024 + decXHi) + ((int64_t)nCtx << 56);
+    const std::pair<int64_t, int> key(word, nAfter);     // (the look-ahead count beside the word: no two plans share a key)
     const bool fmt = precision >= 2;       // split-format tensors: everything a GEMM reads (see gather_gemm_v5.h)
     auto plainF32 = [](int buf) { buf = baseBuf(buf); return buf == BUF_S || buf == BUF_PVPART || buf == BUF_D4 || buf == BUF_COMP; };
     if (fmt && !h->weightsSplit) {
@@ -195,7 +199,7 @@ static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int 
     std::unique_ptr<PlanDev> pd(new PlanDev);
     pd->lastUse = ++h->useClock;
     try {
-        pd->plan.reset(new Plan(h->model, L, precision, h->lanes, decLo, decHi, decXLo, decXHi, nCtx));
+        pd->plan.reset(new Plan(h->model, L, precision, h->lanes, decLo, decHi, decXLo, decXHi, nCtx, nAfter));
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());
     }
@@ -400,9 +404,9 @@ static int build_plan_dev(vsr_sttn* h, int L, int precision, PlanDev** out, int 
         // a long video with ever new mask rows: drop the 16 least recently used plans -- never a promise-free one (decoder bounds all
         // 0: the hot default of its L) and never the one a multi-area call is in the middle of (they are the most recent ones)
         HIPCHK(hipDeviceSynchronize());            // (nothing in flight may still read the tables that go)
-        std::vector<std::pair<uint64_t, int64_t>> byUse;
+        std::vector<std::pair<uint64_t, std::pair<int64_t, int>>> byUse;
         for (const auto& kv : h->plans)
-            if (kv.first % ((int64_t)1 << 40) != 0) byUse.push_back({kv.second->lastUse, kv.first});
+            if (kv.first.first % ((int64_t)1 << 40) != 0) byUse.push_back({kv.second->lastUse, kv.first});
         std::sort(byUse.begin(), byUse.end());
         for (size_t i = 0; i < byUse.size() && i < 16; ++i) h->plans.erase(byUse[i].second);
         if (h->plans.size() >= 48) h->plans.clear();      // only promise-free plans of 48 different lengths: start over
@@ -857,7 +861,8 @@ static void model_cols_of_mask(bool det, int mw, int W, int c0, int c1, int* lo,
 
 static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
                          const int32_t* areas, const int32_t* sel, int nsel, hipStream_t stream, const int32_t* maskRows = nullptr,
-                         const int32_t* maskCols = nullptr, const uint8_t* ctx_dev = nullptr, int nCtx = 0)
+                         const int32_t* maskCols = nullptr, const uint8_t* ctx_dev = nullptr, int nCtx = 0,
+                         const uint8_t* after_dev = nullptr, int nAfter = 0)
 {
     if (!frames_dev || !mask_dev || L <= 0 || H <= 0 || W <= 0 || n_areas < 0 || (n_areas > 0 && !areas))
         return fail(VSR_ERR_ARG, "bad argument");
@@ -867,7 +872,9 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
     const int Ls = (sel && nsel > 0) ? nsel : L;
     // look-back context (vsr_sttn_auto_chunk_ctx, vsr_sttn_det_batch_ctx): the plan's list is the nCtx context frames followed by the Ls selected ones; the
     // context strips are resized in front of them, the blend reads the comp frames behind them and writes frames_dev alone
-    const int Lp = nCtx + Ls;
+    // look-ahead context (the _ctx2 entry points) is the mirror image: nAfter more read-only frames from a pointer of their own, resized behind the
+    // selected ones; nothing of them is blended back
+    const int Lp = nCtx + Ls + nAfter;
     const int32_t* dSel = nullptr;
     if (sel && nsel > 0) {
         for (int i = 0; i < nsel; ++i)
@@ -927,7 +934,7 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
         }
     }
     PlanDev* pd = nullptr;
-    RCCHK(build_plan_dev(h, Lp, h->precision, &pd, decLo[0], decHi[0], decXLo[0], decXHi[0], nCtx));
+    RCCHK(build_plan_dev(h, Lp, h->precision, &pd, decLo[0], decHi[0], decXLo[0], decXHi[0], nCtx, nAfter));
     const int64_t compElems = (int64_t)Lp * mh * mw * 3;
     if (n_areas > 1 && h->compAreasCap < compElems * n_areas) {
         if (h->compAreas) HIPCHK(hipFree(h->compAreas));
@@ -951,11 +958,15 @@ static int strips_common(vsr_sttn* h, bool det, uint8_t* frames_dev, int L, int 
         if (vsr_launch_resize_u8(frames_dev + (int64_t)ymin * W * 3, frameStride, W * 3, W, sh, (uint8_t*)h->bufs[BUF_IN_U8] + (int64_t)nCtx * mh * mw * 3, mw,
                                  mh, Ls, 3, dSel, st->dxofs, st->dialpha, st->dyofs, st->dibeta, stream) != 0)
             return fail(VSR_ERR_HIP, "resize launch failed");
+        if (nAfter > 0 && vsr_launch_resize_u8(after_dev + (int64_t)ymin * W * 3, frameStride, W * 3, W, sh,
+                                               (uint8_t*)h->bufs[BUF_IN_U8] + (int64_t)(nCtx + Ls) * mh * mw * 3, mw, mh, nAfter, 3, nullptr, st->dxofs,
+                                               st->dialpha, st->dyofs, st->dibeta, stream) != 0)
+            return fail(VSR_ERR_HIP, "look-ahead resize launch failed");
         if (det) // cv2.resize(mask_crop, (432, 240)) -- the same strip mask for every frame of the list, context included (frame stride 0)
             if (vsr_launch_resize_u8(mask_dev + (int64_t)ymin * W, 0, W, W, sh, (uint8_t*)h->bufs[BUF_MASK_U8], mw, mh, Lp, 1,
                                      nullptr, st->dxofs, st->dialpha, st->dyofs, st->dibeta, stream) != 0)
                 return fail(VSR_ERR_HIP, "mask resize launch failed");
-        if (k > 0 || attempt > 0) RCCHK(build_plan_dev(h, Lp, attempt ? 0 : h->precision, &pd, decLo[k], decHi[k], decXLo[k], decXHi[k], nCtx));
+        if (k > 0 || attempt > 0) RCCHK(build_plan_dev(h, Lp, attempt ? 0 : h->precision, &pd, decLo[k], decHi[k], decXLo[k], decXHi[k], nCtx, nAfter));
         RCCHK(run_plan(h, pd, stream));
         if (n_areas > 1)
             HIPCHK(hipMemcpyAsync(h->compAreas + compElems * k, h->bufs[BUF_COMP], (size_t)compElems * sizeof(float),
@@ -1004,27 +1015,39 @@ int vsr_sttn_auto_chunk_box(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, in
     return strips_common(h, false, frames_dev, L, H, W, mask_dev, n_areas, areas, sel, nsel, (hipStream_t)stream_, mask_rows, mask_cols);
 }
 
+int vsr_sttn_auto_chunk_ctx2(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
+                             const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const int32_t* sel, int nsel,
+                             const uint8_t* ctx_dev, int n_ctx, const uint8_t* after_dev, int n_after, void* stream_)
+{
+    RCCHK(need_gpu(h));
+    if (h->model.g.variant != VSR_VARIANT_STTN_AUTO) return fail(VSR_ERR_STATE, "not an sttn-auto model");
+    if (n_ctx < 0 || (n_ctx > 0 && !ctx_dev) || n_after < 0 || (n_after > 0 && !after_dev)) return fail(VSR_ERR_ARG, "bad context");
+    return strips_common(h, false, frames_dev, L, H, W, mask_dev, n_areas, areas, sel, nsel, (hipStream_t)stream_, mask_rows, mask_cols,
+                         n_ctx > 0 ? ctx_dev : nullptr, n_ctx, n_after > 0 ? after_dev : nullptr, n_after);
+}
+
 int vsr_sttn_auto_chunk_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
                             const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const int32_t* sel, int nsel,
                             const uint8_t* ctx_dev, int n_ctx, void* stream_)
 {
-    RCCHK(need_gpu(h));
-    if (h->model.g.variant != VSR_VARIANT_STTN_AUTO) return fail(VSR_ERR_STATE, "not an sttn-auto model");
-    if (n_ctx < 0 || (n_ctx > 0 && !ctx_dev)) return fail(VSR_ERR_ARG, "bad context");
-    return strips_common(h, false, frames_dev, L, H, W, mask_dev, n_areas, areas, sel, nsel, (hipStream_t)stream_, mask_rows, mask_cols,
-                         n_ctx > 0 ? ctx_dev : nullptr, n_ctx);
+    return vsr_sttn_auto_chunk_ctx2(h, frames_dev, L, H, W, mask_dev, n_areas, areas, mask_rows, mask_cols, sel, nsel, ctx_dev, n_ctx, nullptr, 0, stream_);
 }
 
-double vsr_sttn_flops_ctx(vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi)
+double vsr_sttn_flops_ctx2(vsr_sttn_t* h, int L, int n_ctx, int n_after, int row_lo, int row_hi, int col_lo, int col_hi)
 {
     if (!h || !h->model.packed_ready() || L <= 0) { fail(VSR_ERR_ARG, "bad argument"); return -1.0; }
     try {
-        Plan p(h->model, L, 0, 1, row_lo, row_hi, col_lo, col_hi, n_ctx);
+        Plan p(h->model, L, 0, 1, row_lo, row_hi, col_lo, col_hi, n_ctx, n_after);
         return p.flops;
     } catch (const std::exception& e) {
         fail(VSR_ERR_ARG, e.what());
         return -1.0;
     }
+}
+
+double vsr_sttn_flops_ctx(vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi)
+{
+    return vsr_sttn_flops_ctx2(h, L, n_ctx, 0, row_lo, row_hi, col_lo, col_hi);
 }
 
 double vsr_sttn_flops_rows(vsr_sttn_t* h, int L, int row_lo, int row_hi)
@@ -1118,15 +1141,22 @@ int vsr_sttn_det_batch_box(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int
     return strips_common(h, true, frames_dev, L, H, W, mask_dev, n_areas, areas, nullptr, 0, (hipStream_t)stream_, mask_rows, mask_cols);
 }
 
+int vsr_sttn_det_batch_ctx2(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
+                            const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const uint8_t* ctx_dev, int n_ctx,
+                            const uint8_t* after_dev, int n_after, void* stream_)
+{
+    RCCHK(need_gpu(h));
+    if (h->model.g.variant != VSR_VARIANT_STTN_DET) return fail(VSR_ERR_STATE, "not an sttn-det model");
+    if (n_ctx < 0 || (n_ctx > 0 && !ctx_dev) || n_after < 0 || (n_after > 0 && !after_dev)) return fail(VSR_ERR_ARG, "bad context");
+    return strips_common(h, true, frames_dev, L, H, W, mask_dev, n_areas, areas, nullptr, 0, (hipStream_t)stream_, mask_rows, mask_cols,
+                         n_ctx > 0 ? ctx_dev : nullptr, n_ctx, n_after > 0 ? after_dev : nullptr, n_after);
+}
+
 int vsr_sttn_det_batch_ctx(vsr_sttn_t* h, uint8_t* frames_dev, int L, int H, int W, const uint8_t* mask_dev, int n_areas,
                            const int32_t* areas, const int32_t* mask_rows, const int32_t* mask_cols, const uint8_t* ctx_dev, int n_ctx,
                            void* stream_)
 {
-    RCCHK(need_gpu(h));
-    if (h->model.g.variant != VSR_VARIANT_STTN_DET) return fail(VSR_ERR_STATE, "not an sttn-det model");
-    if (n_ctx < 0 || (n_ctx > 0 && !ctx_dev)) return fail(VSR_ERR_ARG, "bad context");
-    return strips_common(h, true, frames_dev, L, H, W, mask_dev, n_areas, areas, nullptr, 0, (hipStream_t)stream_, mask_rows, mask_cols,
-                         n_ctx > 0 ? ctx_dev : nullptr, n_ctx);
+    return vsr_sttn_det_batch_ctx2(h, frames_dev, L, H, W, mask_dev, n_areas, areas, mask_rows, mask_cols, ctx_dev, n_ctx, nullptr, 0, stream_);
 }
 
 int vsr_sttn_set_precision(vsr_sttn_t* h, int mode)
@@ -1430,11 +1460,15 @@ int vsr_plan_create_box(const vsr_sttn_t* h, int L, int row_lo, int row_hi, int 
 }
 int vsr_plan_create_ctx(const vsr_sttn_t* h, int L, int n_ctx, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out)
 {
+    return vsr_plan_create_ctx2(h, L, n_ctx, 0, row_lo, row_hi, col_lo, col_hi, out);
+}
+int vsr_plan_create_ctx2(const vsr_sttn_t* h, int L, int n_ctx, int n_after, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out)
+{
     if (!h || !out || L <= 0) return fail(VSR_ERR_ARG, "bad argument");
     if (!h->model.packed_ready()) return fail(VSR_ERR_STATE, "model not finalized");
     try {
         std::unique_ptr<vsr_plan> p(new vsr_plan);
-        p->plan.reset(new Plan(h->model, L, 0, h->lanes, row_lo, row_hi, col_lo, col_hi, n_ctx));
+        p->plan.reset(new Plan(h->model, L, 0, h->lanes, row_lo, row_hi, col_lo, col_hi, n_ctx, n_after));
         *out = p.release();
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());

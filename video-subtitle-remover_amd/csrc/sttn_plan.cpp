@@ -755,9 +755,12 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
     const int T = (int)ids.size(), nn = (int)neighbors.size();
     // look-back context (Plan::nCtx): the neighbours are ascending, so the read-only ones are the first q0 of them; the last block's
     // query rows and the decoder are built for the nw written ones, which the window's buffers then hold from frame 0 on
-    int q0 = 0;
+    // look-ahead context (Plan::nAfter) is the mirror image: the read-only neighbours at the other end are those from q1 on, so the
+    // written ones are the contiguous run [q0, q1)
+    int q0 = 0, q1 = nn;
     while (q0 < nn && neighbors[q0] < nCtx) ++q0;
-    const int nw = nn - q0;
+    while (q1 > q0 && neighbors[q1 - 1] >= L - nAfter) --q1;
+    const int nw = q1 - q0;
     const Act feats{BUF_FEATS, L, fh, fw, C, 2};
     const Act x0{lb(BUF_X0), T, fh, fw, C, 2}, x1{lb(BUF_X1), T, fh, fw, C, 2};
     const Act att{lb(BUF_ATT), T, fh, fw, C, 1}, f1{lb(BUF_F1), T, fh, fw, C, 1};
@@ -832,7 +835,7 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         // conv needs one more row of the first conv's output on each side, the first (dilation 2) two more of the out-conv's, the
         // out-conv one more of the attention output, and the attention output rows belong to the patches that touch them.
         // (a window with context neighbours is trimmed whatever the switch says: the decoder addresses the written frames from 0 on)
-        const bool last = (tu_.trimLastBlock || q0 > 0) && b == g.blocks - 1;
+        const bool last = (tu_.trimLastBlock || nw < nn) && b == g.blocks - 1;
         const int Tq = last ? nw : T, qFirst = last ? q0 : 0;
         const int r2lo = last ? lastLo : 0, r2hi = last ? lastHi : fh;                       // ffn.2 output = the block's output
         auto wide = [&](int lo, int hi, int by, int& olo, int& ohi) { olo = lo - by > 0 ? lo - by : 0; ohi = hi + by < fh ? hi + by : fh; };
@@ -857,7 +860,7 @@ void Plan::buildWindow(const std::vector<int>& neighbors, const std::vector<int>
         curIds = idT;
     }
 
-    // decoder on the neighbour frames only (sttn_auto_inpaint.py:150; auto_sttn.py:87-95,118-127) -- the written ones (nw = nn without the context frames)
+    // decoder on the neighbour frames only (sttn_auto_inpaint.py:150; auto_sttn.py:87-95,118-127) -- the written ones (nw = nn without the context frames of either end)
     const Act up1{lb(BUF_UP1), nw, 2 * fh, 2 * fw, C, 1}, d1{lb(BUF_D1), nw, 2 * fh, 2 * fw, 128, 1};
     const Act d2{lb(BUF_D2), nw, 2 * fh, 2 * fw, 64, 0}, up2{lb(BUF_UP2), nw, mh, mw, 64, 1}, d3{lb(BUF_D3), nw, mh, mw, 64, 1};
     const std::vector<int> idN = iota(nw);
@@ -1016,13 +1019,14 @@ void Plan::decoder_bounds(const Geometry& g, int precision, int decLo_, int decH
     *lo = decLo; *hi = decHi; *xlo = decXLo; *xhi = decXHi;
 }
 
-Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, int decHi_, int decXLo_, int decXHi_, int nCtx_)
-    : L(L_), nCtx(nCtx_), precision(precision_), lanes(lanes_ < 1 ? 1 : (lanes_ > kMaxLanes ? kMaxLanes : lanes_)), g(model.g), m_(model), tu_(Tuning::get(precision_))
+Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, int decHi_, int decXLo_, int decXHi_, int nCtx_, int nAfter_)
+    : L(L_), nCtx(nCtx_), nAfter(nAfter_), precision(precision_), lanes(lanes_ < 1 ? 1 : (lanes_ > kMaxLanes ? kMaxLanes : lanes_)), g(model.g), m_(model), tu_(Tuning::get(precision_))
 {
     decoder_bounds(g, precision_, decLo_, decHi_, decXLo_, decXHi_, &decLo, &decHi, &decXLo, &decXHi);
     if (!model.packed_ready()) throw std::runtime_error("model weights are not packed");
     if (L <= 0) throw std::runtime_error("empty frame list");
     if (nCtx < 0 || nCtx >= L) throw std::runtime_error("context frames: 0 <= n_ctx < frames of the list");
+    if (nAfter < 0 || nCtx + nAfter >= L) throw std::runtime_error("context frames: 0 <= n_after, n_ctx + n_after < frames of the list (nothing left to write)");
     bufElems.assign(BUF_COUNT, 0);
     bufElems[BUF_WEIGHTS] = (int64_t)model.packed.size();
     const int mh = g.modelH, mw = g.modelW, fh = g.featH, fw = g.featW, C = g.channels;
@@ -1119,6 +1123,7 @@ Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, i
             if (!inN) refs.push_back(i);
         }
         if (neighbors.back() < nCtx) continue;     // no written neighbour: nothing of this window is read (Plan::nCtx)
+        if (neighbors.front() >= L - nAfter) continue;     // ... and its mirror: every neighbour is look-ahead context (Plan::nAfter)
         // windows are independent until OP_DECODE_OUT averages their frames into BUF_COMP (in window order): window w works in
         // lane w % lanes' buffers and is issued on that lane's stream
         lane_ = nwindows % lanes;
@@ -1133,7 +1138,7 @@ Plan::Plan(const Model& model, int L_, int precision_, int lanes_, int decLo_, i
     flopsExecuted = 0;
     for (const Op& op : ops) flopsExecuted += op.flopsExecuted >= 0 ? op.flopsExecuted : op.flops;
     // (the reference runs the whole list: what it spends is the plain plan's count, dropped windows and context decodes included)
-    if (nCtx > 0) refFlops = Plan(model, L_, precision_, 1, decLo_, decHi_, decXLo_, decXHi_).refFlops;
+    if (nCtx > 0 || nAfter > 0) refFlops = Plan(model, L_, precision_, 1, decLo_, decHi_, decXLo_, decXHi_).refFlops;
 }
 
 // ------------------------------------------------------------------------------------

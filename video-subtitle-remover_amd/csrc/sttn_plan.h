@@ -214,7 +214,12 @@ public:
     // sttn-det needs no op of its own for this: its three extras index frames by LIST index -- enc.im2col pre-masks frame f with mask
     // plane f of BUF_MASK_U8 (sized for the whole list), dec.out blends comp frame tFrameIdx[i] with input frame and mask plane
     // tFrameIdx[i] over every row -- and the decode ops' frame tables name written frames only.
-    Plan(const Model& model, int L, int precision = 0, int lanes = 1, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0, int nCtx = 0);
+    // nAfter: the mirror image, the LAST nAfter frames of the list are look-ahead context (vsr_sttn_auto_chunk_ctx2, vsr_sttn_det_batch_ctx2),
+    // read and never written in the same way.  A window's neighbours are ascending, so its written neighbours are one contiguous
+    // run [q0, q1) of them (buildWindow); a window whose neighbours all lie in the suffix is not built.  nAfter = 0 builds the plan
+    // of nCtx alone op for op, both 0 the plain plan.  nCtx + nAfter < L: something is written.
+    Plan(const Model& model, int L, int precision = 0, int lanes = 1, int decLo = 0, int decHi = 0, int decXLo = 0, int decXHi = 0, int nCtx = 0,
+         int nAfter = 0);
     // the bounds a plan with these arguments decodes: clipped to the image and widened to whole blocks of the output conv (all 0 = the
     // whole image: no promise, or the per-pixel form of the output conv).  Needs no plan: vsr_sttn_decode_rows asks once per area.
     static void decoder_bounds(const Geometry& g, int precision, int decLo, int decHi, int decXLo, int decXHi, int* lo, int* hi, int* xlo, int* xhi);
@@ -222,6 +227,7 @@ public:
     int decXLo = 0, decXHi = 0;          // ... to whole 4-column blocks
     int L;
     int nCtx = 0;                        // frames [0, nCtx) are read-only context; compCount of those stays 0
+    int nAfter = 0;                      // frames [L - nAfter, L) likewise
     int precision;
     int lanes;                           // 1 .. kMaxLanes: window w runs on lane w % lanes
     int firstWindowOp = -1;              // index of the first op that is not the encoder's: lane 1 may start once everything before it is done
@@ -248,7 +254,7 @@ private:
                  const std::vector<int>* resIds, int ylo = 0, int yhi = -1,      // [ylo, yhi): output rows computed (stride 1; default all)
                  int xlo = 0, int xhi = -1);                                       // [xlo, xhi): output columns computed (default all)
     // [attLo, attHi) x [attXLo, attXHi): feature rows / columns of the output that are read
-    // qFirst: the query frames are frames [qFirst, qFirst + Tq) of the T (their rows of the attention output are stored from frame 0 on)
+    // qFirst: the query frames are frames [qFirst, qFirst + Tq) of the T -- the written run [q0, q1) of a window with context neighbours (their rows of the attention output are stored from frame 0 on)
     void addAttention(int Tq, int T, const BlockW& bw, int attLo = 0, int attHi = -1, int attXLo = 0, int attXHi = -1, int qkvBuf = -1,
                       const std::vector<int>* fids = nullptr, int qFirst = 0);
     void buildWindow(const std::vector<int>& neighbors, const std::vector<int>& refs,

@@ -283,22 +283,38 @@ class SttnEngine(AccuracyGuard):
             frames_dev.copy_(exact)
         return frames_dev
 
-    def auto_chunk(self, frames_dev, mask_dev, areas, sel=None, decode_rows=True, mask_host=None, context=None):
+    def auto_chunk(self, frames_dev, mask_dev, areas, sel=None, decode_rows=True, mask_host=None, context=None, lookahead=None):
         """One chunk of STTNAutoInpaint.__call__, in place on frames_dev uint8 [L,H,W,3] BGR.  The rows of every strip that hold the
         mask go along (mask_rows): the decoder then computes only what the blend reads -- same frames (vsr_sttn_auto_chunk_rows).
         context (not in the reference): uint8 [n_ctx,H,W,3] on the device, the source frames in front of the chunk.  The chunk comes
         out as the last L frames of the list context ++ frames would, bit for bit; the context tensor is only read (and is the
-        same tensor in the accuracy guard's exact re-run: the guard clones and compares frames_dev alone)."""
-        return self._guarded_in_place(lambda t: self._auto_chunk(t, mask_dev, areas, sel, decode_rows, mask_host, context), frames_dev)
+        same tensor in the accuracy guard's exact re-run: the guard clones and compares frames_dev alone).
+        lookahead (not in the reference): uint8 [n_after,H,W,3], the source frames BEHIND the chunk, the mirror image: the chunk comes
+        out as frames [n_ctx, n_ctx + L) of the list context ++ frames ++ lookahead would, bit for bit (vsr_sttn_auto_chunk_ctx2)."""
+        return self._guarded_in_place(lambda t: self._auto_chunk(t, mask_dev, areas, sel, decode_rows, mask_host, context, lookahead), frames_dev)
 
-    def context_flops(self, L, n_ctx, rows=(0, 0), cols=(0, 0)):
-        """FLOPs of the plan of a list of L frames (context included) whose first n_ctx are context (vsr_sttn_flops_ctx)"""
-        v = lib.vsr_sttn_flops_ctx(self._h, int(L), int(n_ctx), int(rows[0]), int(rows[1]), int(cols[0]), int(cols[1]))
+    def context_flops(self, L, n_ctx, rows=(0, 0), cols=(0, 0), n_after=0):
+        """FLOPs of the plan of a list of L frames (context included) whose first n_ctx and last n_after are context (vsr_sttn_flops_ctx2)"""
+        v = lib.vsr_sttn_flops_ctx2(self._h, int(L), int(n_ctx), int(n_after), int(rows[0]), int(rows[1]), int(cols[0]), int(cols[1]))
         if v < 0:
             raise _lib.VsrError(_lib.VSR_ERR_ARG, _lib.last_error())
         return v
 
-    def _auto_chunk(self, frames_dev, mask_dev, areas, sel=None, decode_rows=True, mask_host=None, context=None):
+    @staticmethod
+    def _context_args(frames_dev, context, lookahead, unit):
+        """(pointer, count) of each context tensor for the _ctx2 entry points, after the checks both kinds share"""
+        out = []
+        for t, what in ((context, "context"), (lookahead, "look-ahead")):
+            if t is None:
+                out += [None, 0]
+                continue
+            assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.device == frames_dev.device
+            if tuple(t.shape[1:]) != tuple(frames_dev.shape[1:]):
+                raise ValueError(f"{what} frames {tuple(t.shape[1:])} do not have the {unit}'s geometry {tuple(frames_dev.shape[1:])}")
+            out += [C.c_void_p(t.data_ptr()), int(t.shape[0])]
+        return out
+
+    def _auto_chunk(self, frames_dev, mask_dev, areas, sel=None, decode_rows=True, mask_host=None, context=None, lookahead=None):
         assert frames_dev.dtype == torch.uint8 and frames_dev.is_cuda and frames_dev.is_contiguous()
         assert mask_dev.dtype == torch.uint8 and mask_dev.is_cuda and mask_dev.is_contiguous()
         L, H, W, _ = frames_dev.shape
@@ -309,6 +325,20 @@ class SttnEngine(AccuracyGuard):
         # (mask_host: the caller's numpy copy of the mask, when it has one -- the rows are then read off it)
         self._check_mask_host(mask_host, mask_dev)
         rows = np.ascontiguousarray(self.mask_rows(mask_dev if mask_host is None else mask_host, ar)) if decode_rows else np.zeros((ar.shape[0], 2), dtype=np.int32)
+        if lookahead is not None and lookahead.shape[0] == 0:
+            lookahead = None
+        if lookahead is not None:
+            ctx_args = self._context_args(frames_dev, context, lookahead, "chunk")
+            cols = None
+            if decode_rows and switches.on("VSR_DECODE_COLS"):
+                cols = np.ascontiguousarray(self.mask_cols(mask_dev if mask_host is None else mask_host, ar))
+            with torch.cuda.device(frames_dev.device):
+                check(lib.vsr_sttn_auto_chunk_ctx2(
+                    self._h, C.c_void_p(frames_dev.data_ptr()), L, H, W, C.c_void_p(mask_dev.data_ptr()), ar.shape[0],
+                    ar.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p), None if cols is None else cols.ctypes.data_as(C.c_void_p),
+                    None if sel_arr is None else sel_arr.ctypes.data_as(C.c_void_p),
+                    0 if sel_arr is None else int(sel_arr.size), *ctx_args, _stream_ptr()))
+            return frames_dev
         if context is not None:      # (an empty one too: n_ctx = 0 is the entry point's plain call)
             assert context.dtype == torch.uint8 and context.is_cuda and context.is_contiguous() and context.device == frames_dev.device
             if tuple(context.shape[1:]) != (H, W, 3):
@@ -361,22 +391,36 @@ class SttnEngine(AccuracyGuard):
                                            C.c_void_p(comp.data_ptr()), counts.ctypes.data_as(C.c_void_p), _stream_ptr()))
         return comp, counts
 
-    def det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None, context=None):
+    def det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None, context=None, lookahead=None):
         """STTNDetInpaint.__call__ on one batch, in place on frames_dev uint8 [L,H,W,3] BGR; mask_dev raw 0/255 [H,W].  The rows of
         every strip that hold the mask go along (mask_rows): the decoder computes only the model rows the prediction is taken from
         (vsr_sttn_det_batch_rows) -- same frames; decode_rows=False: no promise.
         context (not in the reference): uint8 [n_ctx,H,W,3] on the device, the source frames in front of the batch.  The batch comes
         out as the last L frames of the list context ++ frames would, bit for bit; the context tensor is only read (and is the
-        same tensor in the accuracy guard's exact re-run: the guard clones and compares frames_dev alone)."""
-        return self._guarded_in_place(lambda t: self._det_batch(t, mask_dev, areas, decode_rows, mask_host, context), frames_dev)
+        same tensor in the accuracy guard's exact re-run: the guard clones and compares frames_dev alone).
+        lookahead (not in the reference): uint8 [n_after,H,W,3], the source frames BEHIND the batch, the mirror image: the batch comes
+        out as frames [n_ctx, n_ctx + L) of the list context ++ frames ++ lookahead would, bit for bit (vsr_sttn_det_batch_ctx2)."""
+        return self._guarded_in_place(lambda t: self._det_batch(t, mask_dev, areas, decode_rows, mask_host, context, lookahead), frames_dev)
 
-    def _det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None, context=None):
+    def _det_batch(self, frames_dev, mask_dev, areas, decode_rows=True, mask_host=None, context=None, lookahead=None):
         assert frames_dev.dtype == torch.uint8 and frames_dev.is_cuda and frames_dev.is_contiguous()
         assert mask_dev.dtype == torch.uint8 and mask_dev.is_cuda and mask_dev.is_contiguous()
         L, H, W, _ = frames_dev.shape
         ar = np.ascontiguousarray(np.asarray(areas, dtype=np.int32).reshape(-1, 4))
         self._check_mask_host(mask_host, mask_dev)
         rows = np.ascontiguousarray(self.mask_rows(mask_dev if mask_host is None else mask_host, ar)) if decode_rows else np.zeros((ar.shape[0], 2), dtype=np.int32)
+        if lookahead is not None and lookahead.shape[0] == 0:
+            lookahead = None
+        if lookahead is not None:
+            ctx_args = self._context_args(frames_dev, context, lookahead, "batch")
+            cols = None
+            if decode_rows and switches.on("VSR_DECODE_COLS"):
+                cols = np.ascontiguousarray(self.mask_cols(mask_dev if mask_host is None else mask_host, ar))
+            with torch.cuda.device(frames_dev.device):
+                check(lib.vsr_sttn_det_batch_ctx2(self._h, C.c_void_p(frames_dev.data_ptr()), L, H, W, C.c_void_p(mask_dev.data_ptr()),
+                                                  ar.shape[0], ar.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p),
+                                                  None if cols is None else cols.ctypes.data_as(C.c_void_p), *ctx_args, _stream_ptr()))
+            return frames_dev
         if context is not None:      # (an empty one too: n_ctx = 0 is the entry point's plain call)
             assert context.dtype == torch.uint8 and context.is_cuda and context.is_contiguous() and context.device == frames_dev.device
             if tuple(context.shape[1:]) != (H, W, 3):
