@@ -658,6 +658,29 @@ int vsr_feather_composite(uint8_t* frames_dev, int64_t frame_stride, const uint8
                           const uint8_t* alpha_dev, int n, int H, int W, int feather, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Regrain (--regrain P, csrc/regrain_kernels.hip; the statement is tests/_regrain_statement.py, the design DESIGN.md 4.12): the
+ * source's grain, measured in a ring around the composite mask, put back inside the inpainted pixels.  Stateless; all pointers are
+ * device pointers, all work is issued on `stream`, nothing waits for the device.  The frames hold `rows` rows of the H x W picture
+ * starting at its row y0 (the whole picture: y0 = 0, rows = H), rows * W * 3 contiguous bytes each at any alignment, frame f at
+ * base + f * stride bytes; [c0, c1) are the rows of the picture that hold a non-zero of the mask (a wider range costs time only).
+ * Bad arguments (a null pointer, H or W <= 0, H * W * 3 >= 2^31, rows outside the frame, a stride smaller than a frame, n < 0,
+ * P outside 0..200) return VSR_ERR_ARG and launch nothing; n == 0 is success without a launch.
+ * ------------------------------------------------------------------------------------- */
+/* cmask_dev uint8 [H][W] (non-zero: the plugin blends here), sample rows [r0, r1) -> map_dev uint8 [H][W]: bit 0 = E (3x3 neighbourhood
+ * all zero, a non-zero within Chebyshev distance 16), bit 1 = I (3x3 neighbourhood all non-zero), both only where r0 + 1 <= y < r1 - 1
+ * and 1 <= x < W - 1; bit 2 = cmask != 0.  counts_dev[0] = |E|, counts_dev[1] = |I| (two 64-bit words, zeroed by the call). */
+int vsr_regrain_sets(const uint8_t* cmask_dev, int H, int W, int r0, int r1, uint8_t* map_dev, uint64_t* counts_dev, void* stream);
+/* stats_dev: four 64-bit words per frame (zeroed by the call): the sum over E of L(src), the sum over I of L(frames), the number of
+ * pixels of the mask where frames != src, unused.  L = the sum over the channels of |[[1,-2,1],[-2,4,-2],[1,-2,1]] * x|. */
+int vsr_regrain_measure(const uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride,
+                        const uint8_t* map_dev, int n, int H, int W, int y0, int rows, int c0, int c1, uint64_t* stats_dev, void* stream);
+/* IN PLACE on the frames, reading counts_dev and stats_dev on the device: a frame with |E| or |I| zero or no changed pixel is left as
+ * it is; else every pixel of the mask gets clamp(fill + ((r * P * 60701 * z + 2^39) >> 40)) on its three channels, r the integer square
+ * root of the deficit in quadrature and z the hash of the pixel's position in the picture and the frame's seed. */
+int vsr_regrain_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* map_dev, const uint64_t* counts_dev,
+                      const uint64_t* stats_dev, int n, int H, int W, int y0, int rows, int c0, int c1, int percent, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),
  * with symbolic buffers and the offset tables -- replayed on the CPU by tests/.
  * ------------------------------------------------------------------------------------- */

@@ -66,6 +66,10 @@ class LamaInpaint:
         m = np.asarray(input_mask)
         return (m.reshape(m.shape[0], m.shape[1]) != 0).astype(np.uint8)
 
+    def sample_rows(self, input_mask):
+        """(r0, r1): the rows --regrain samples the source's grain in (tools/regrain.py): the whole frame"""
+        return 0, int(np.asarray(input_mask).shape[0])
+
     def inpaint(self, image, mask):
         """the single picture and propainter's single frames (main.py:217-224,364); under --seam-feather a one-frame plugin call"""
         return seam_feather.plugin_call(self, self._inpaint_one, [image], mask, self.engine.device)[0]

@@ -68,6 +68,10 @@ class OpenCVInpaint:
         """uint8 [H,W]: the pixels this plugin fills (--seam-feather, tools/seam_feather.py): mask != 0"""
         return (_mask2d(input_mask) != 0).astype(np.uint8)
 
+    def sample_rows(self, input_mask):
+        """(r0, r1): the rows --regrain samples the source's grain in (tools/regrain.py): the whole frame"""
+        return 0, int(np.asarray(input_mask).shape[0])
+
     def __call__(self, input_frames, input_mask):
         """input_frames: the reference's list of HxWx3 uint8 BGR arrays (fresh arrays come back, inputs untouched), or -- the
         HBM-resident loop of main.SubtitleRemover, tools/resident.py -- a uint8 [n,H,W,3] device tensor, which is inpainted IN

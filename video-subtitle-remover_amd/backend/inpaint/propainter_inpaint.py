@@ -478,6 +478,10 @@ class PropainterInpaint:
             out[y0:y1, x0:x1] |= read_mask(mask[y0:y1, x0:x1, :], 1, self.mask_dilation, self.mask_dilation)[1]
         return out
 
+    def sample_rows(self, input_mask):
+        """(r0, r1): the rows --regrain samples the source's grain in (tools/regrain.py): the whole frame"""
+        return 0, int(np.asarray(input_mask).shape[0])
+
     def __call__(self, input_frames, input_mask):
         """(--seam-feather: the call ends with the feathered composite, tools/seam_feather.py)"""
         return seam_feather.plugin_call(self, self._call, input_frames, input_mask, self.dev)

@@ -40,6 +40,10 @@ class STTNDetInpaint:
         """uint8 [H,W]: the pixels this plugin blends its prediction under (--seam-feather, tools/seam_feather.py): mask != 0"""
         return (np.asarray(input_mask) != 0).astype(np.uint8)
 
+    def sample_rows(self, input_mask):
+        """(r0, r1): the rows --regrain samples the source's grain in (tools/regrain.py): the whole frame"""
+        return 0, int(np.asarray(input_mask).shape[0])
+
     def __call__(self, input_frames, input_mask, context=None, lookahead=None):
         """The call below; under --seam-feather it ends with the feathered composite (tools/seam_feather.py): the batch comes back
         mask-exact, the context frames are read-only as before and take no part."""

@@ -295,6 +295,7 @@ class SubtitleRemover:
         from .tools import seam_feather
 
         seam_feather.refuse_ranks(dist)                                                 # --seam-feather: bad values and several ranks, before any frame is read
+        seam_feather.regrain.refuse_ranks(dist)                                         # --regrain: the same
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), propainter_inpaint)
         if single_frame_inpaint is None:
@@ -438,6 +439,7 @@ class SubtitleRemover:
         from .tools import seam_feather
 
         seam_feather.refuse_ranks(self._distributed())                                  # --seam-feather: bad values and several ranks, before any frame is read
+        seam_feather.regrain.refuse_ranks(self._distributed())                          # --regrain: the same
         max_load = config.getSttnMaxLoadNum()
         n_context, scene_split, n_ahead = (0, False, 0)
         if getattr(model, "accepts_context", False):
@@ -664,6 +666,7 @@ class SubtitleRemover:
 
         start_time = time.time()
         seam_feather.refuse_ranks(self._distributed())                   # --seam-feather: a bad value or several ranks fail before any work is done
+        seam_feather.regrain.refuse_ranks(self._distributed())           # --regrain: the same
         if self._video_writer is None and self.is_path:
             self._y4m_like()                                             # a sink that cannot be made fails before any work is done
         if len(self.sub_areas) == 0:
@@ -718,6 +721,8 @@ def main(argv=None):
         os.environ["VSR_STTN_LOOKAHEAD"] = str(args.sttn_lookahead)
     if args.seam_feather is not None:
         os.environ["VSR_SEAM_FEATHER"] = str(args.seam_feather)
+    if args.regrain is not None:
+        os.environ["VSR_REGRAIN"] = str(args.regrain)
     sr = SubtitleRemover(args.input)
     sr.sub_areas = [tuple(c) for c in args.subtitle_area_coords]
     if args.output is not None:

@@ -39,6 +39,10 @@ def build_parser():
     parser.add_argument("--seam-feather", type=int, default=None, metavar="F",
                         help="every mode: outside the pixels a plugin blends under, the written frame is the source bit for bit; inside, "
                              "the fill ramps in over F pixels (1 = hard composite, 0 = off, at most 64); one process; sets VSR_SEAM_FEATHER")
+    # not in the reference: every mode puts the source's grain back inside the pixels it inpainted (tools/regrain.py)
+    parser.add_argument("--regrain", type=int, default=None, metavar="P",
+                        help="every mode: measure the source's noise in a ring around the inpainted pixels and add P percent of what the "
+                             "fill lacks back inside them (100 = match the source, 0 = off, at most 200); one process; sets VSR_REGRAIN")
     return parser
 
 
@@ -52,6 +56,13 @@ def parse_args(argv=None):
             feather_option(args.seam_feather)
         except ValueError as e:
             parser.error(f"--seam-feather: {e}")
+    if args.regrain is not None:
+        from .regrain import regrain_option
+
+        try:
+            regrain_option(args.regrain)
+        except ValueError as e:
+            parser.error(f"--regrain: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

@@ -20,6 +20,9 @@ propainter's single-frame LaMa) gets it without knowing.  With F > 0, a non-empt
     4. launches vsr_feather_composite on the same stream, which the body's result is ordered on.
 
 The list form uploads once, runs the device form and downloads once.  Several ranks are refused (refuse_ranks) before any work.
+
+--regrain P (tools/regrain.py) lives in the same two calls and shares the clone: with P > 0 the fill is regrained between
+steps 3 and 4, out = composite(regrain(fill), src, d, F); with F = 0 and P > 0 steps 1 and 4 fall away.  Both off: the body alone.
 """
 import collections
 import ctypes as C
@@ -27,6 +30,8 @@ import os
 import threading
 
 import numpy as np
+
+from . import regrain
 
 MAX_FEATHER = 64
 ENV = "VSR_SEAM_FEATHER"
@@ -121,24 +126,32 @@ def composite(frames, src, d, feather):
     return frames
 
 
-def device_call(frames, cmask, body, feather, rows=None):
+def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None):
     """body(frames) inpaints the device tensor `frames` in place (today's call); with F > 0 and a non-empty composite mask the frames
     come back as the definition's.  cmask: the FULL-frame composite mask (host uint8) or a callable that makes it; rows = (y_lo, y_hi):
     `frames` holds these rows of the frame only (sttn-auto's strip rows) -- d is computed on the full frame and sliced, so a mask that
-    touches the first or last of the rows ramps as it does in the whole frame."""
-    if not feather or frames.shape[0] == 0:
+    touches the first or last of the rows ramps as it does in the whole frame.
+    grain = P of --regrain (tools/regrain.py), sample_rows = the plugin's (None: the whole frame): with P > 0 the fill is regrained
+    against the same source clone before the composite, out = composite(regrain(fill), src, d, F); with F = 0 regrain alone."""
+    if not (feather or grain) or frames.shape[0] == 0:
         return body(frames)
     cm = cmask() if callable(cmask) else cmask
     if not cm.any():
         return body(frames)
     import torch
 
-    d = alpha(cm, feather, frames.device)
-    if rows is not None:
-        d = d[rows[0]:rows[1]]
+    d = None
+    if feather:
+        d = alpha(cm, feather, frames.device)
+        if rows is not None:
+            d = d[rows[0]:rows[1]]
+    sets = regrain.sets(cm, (0, cm.shape[0]) if sample_rows is None else sample_rows, frames.device) if grain else None
     src = frames.clone(memory_format=torch.contiguous_format)
     out = body(frames)
-    composite(frames, src, d, feather)
+    if grain:
+        regrain.apply(frames, src, sets, grain, y0=0 if rows is None else rows[0])
+    if feather:
+        composite(frames, src, d, feather)
     return frames if out is None else out
 
 
@@ -150,28 +163,33 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
     kw = {} if context is None else {"context": context}
     if lookahead is not None:
         kw["lookahead"] = lookahead
-    f = feather_option()
-    if not f:
+    f, g = feather_option(), regrain.regrain_option()
+    if not (f or g):
         return body(input_frames, input_mask, **kw)
     import torch
 
+    sample_rows = plugin.sample_rows(input_mask) if g else None
     if isinstance(input_frames, torch.Tensor):
-        return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda t: body(t, input_mask, **kw), f)
+        return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda t: body(t, input_mask, **kw), f,
+                           grain=g, sample_rows=sample_rows)
     if len(input_frames) == 0:
         return body(input_frames, input_mask, **kw)
     cm = plugin.composite_mask(input_mask)
     if not cm.any():
         return body(input_frames, input_mask, **kw)
     if not getattr(plugin, "accepts_device_frames", False):
-        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the composite
+        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the regrain and the composite
         fill = body(input_frames, input_mask, **kw)
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(fill))).to(device)
         src = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
-        composite(frames, src, alpha(cm, f, frames.device), f)
+        if g:
+            regrain.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), g)
+        if f:
+            composite(frames, src, alpha(cm, f, frames.device), f)
     else:
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
         kw = {name: torch.from_numpy(np.ascontiguousarray(np.stack(c))).to(device)
               for name, c in (("context", context), ("lookahead", lookahead)) if c is not None and len(c)}
-        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f)
+        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f, grain=g, sample_rows=sample_rows)
     out = frames.cpu().numpy()
     return [out[i] for i in range(out.shape[0])]
