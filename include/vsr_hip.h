@@ -681,6 +681,27 @@ int vsr_regrain_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* 
                       const uint64_t* stats_dev, int n, int H, int W, int y0, int rows, int c0, int c1, int percent, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Deflicker (--deflicker R, csrc/deflicker_kernels.hip; the statement is tests/_deflicker_statement.py, the design DESIGN.md 4.13): the
+ * fill steadied over time inside the inpainted pixels of one call's frames, gated by how much the source moved in the ring around
+ * them.  Stateless; all pointers are device pointers, all work is issued on `stream`, nothing waits for the device.  Frames, rows, y0,
+ * [c0, c1) and map_dev (vsr_regrain_sets) are regrain's; R is the radius of the window in frames.  Bad arguments (a null pointer, H or
+ * W <= 0, H * W * 3 >= 2^31, rows outside the frame, a stride smaller than a frame, n < 0, R outside 0..8) return VSR_ERR_ARG and
+ * launch nothing; n == 0 or R == 0 is success without a launch.
+ * ------------------------------------------------------------------------------------- */
+/* pairs_dev: R 64-bit words per frame (zeroed by the call): pairs[t][k-1] = the sum over E (bit 0 of the map) and the channels of
+ * |src_t - src_{t+k}|, 1 <= k <= R, t + k < n. */
+int vsr_deflicker_pairs(const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* map_dev, int n, int H, int W, int y0, int rows,
+                        int c0, int c1, int R, uint64_t* pairs_dev, void* stream);
+/* IN PLACE on the frames, reading counts_dev (vsr_regrain_sets), stats_dev (vsr_regrain_measure of the frames against their source) and
+ * pairs_dev on the device.  snap_dev: a copy of the frames' local rows [max(c0 - y0, 0), min(c1 - y0, rows)) (the unsmoothed fill),
+ * frame f at snap_dev + f * snap_stride, at any alignment.  Per pair the weight a = clamp((16 (4 m - X)) / (3 m), 0, 16), m = 3 |E|,
+ * X = max(0, pairs - ((15447 (A_t + A_s)) >> 17)), 0 if either frame has no changed pixel; per pixel of the mask in a changed frame
+ * (16 * 24 * fill_t + sum a (24 - D) fill_s + den / 2) / den over the neighbours |s - t| <= R with D = max_c |fill_s - fill_t| < 24. */
+int vsr_deflicker_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* snap_dev, int64_t snap_stride, const uint8_t* map_dev,
+                        const uint64_t* counts_dev, const uint64_t* stats_dev, const uint64_t* pairs_dev, int n, int H, int W, int y0,
+                        int rows, int c0, int c1, int R, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),
  * with symbolic buffers and the offset tables -- replayed on the CPU by tests/.
  * ------------------------------------------------------------------------------------- */

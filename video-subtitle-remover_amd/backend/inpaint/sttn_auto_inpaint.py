@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ..config import config
-from ..tools import regrain, seam_feather
+from ..tools import deflicker, regrain, seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask, is_frame_number_in_ab_sections, threshold_mask
 from ..tools.video_io import ArrayWriter, device_bgr_to_planes, device_planes_to_bgr, open_video
 from ...engine import SttnEngine
@@ -80,8 +80,8 @@ class STTNInpaint:
         return (min(a[0] for a in areas), max(a[1] for a in areas)) if areas else (0, 0)
 
     def auto_chunk(self, frames_dev, mask_dev, areas, cmask=None, rows=None, **kw):
-        """SttnEngine.auto_chunk, where all three chunk loops and __call__ end.  cmask: None (--seam-feather and --regrain off: the
-        engine call and nothing else), or the full-frame composite mask; rows = (y_lo, y_hi): frames_dev holds these rows of the frames
+        """SttnEngine.auto_chunk, where all three chunk loops and __call__ end.  cmask: None (--seam-feather, --regrain and --deflicker
+        off: the engine call and nothing else), or the full-frame composite mask; rows = (y_lo, y_hi): frames_dev holds these rows of the frames
         only, the distance is taken on the full frame and sliced (tools/seam_feather.device_call).  Context frames (kw) are read-only.
         --regrain samples in the hull of `areas`' rows (sample_rows, here from the areas the caller already has)."""
         if cmask is None:
@@ -89,7 +89,8 @@ class STTNInpaint:
         y0 = 0 if rows is None else rows[0]
         hull = (y0 + min(a[0] for a in areas), y0 + max(a[1] for a in areas)) if len(areas) else (0, 0)
         return seam_feather.device_call(frames_dev, cmask, lambda t: self.engine.auto_chunk(t, mask_dev, areas, **kw),
-                                        seam_feather.feather_option(), rows=rows, grain=regrain.regrain_option(), sample_rows=hull)
+                                        seam_feather.feather_option(), rows=rows, grain=regrain.regrain_option(), sample_rows=hull,
+                                        flicker=deflicker.deflicker_option())
 
     def __call__(self, input_frames, input_mask):
         mask = threshold_mask(input_mask)
@@ -101,7 +102,8 @@ class STTNInpaint:
         dev = self.engine.device
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(dev, non_blocking=True)
         dmask = torch.from_numpy(np.ascontiguousarray(mask[:, :, 0])).to(dev, non_blocking=True)
-        cmask = self.composite_mask(mask, thresholded=True) if (seam_feather.feather_option() or regrain.regrain_option()) else None
+        wanted = seam_feather.feather_option() or regrain.regrain_option() or deflicker.deflicker_option()
+        cmask = self.composite_mask(mask, thresholded=True) if wanted else None
         self.auto_chunk(frames, dmask, inpaint_area, cmask=cmask, mask_host=mask[:, :, 0])
         out = frames.cpu().numpy()
         return [out[i] for i in range(out.shape[0])]
@@ -182,6 +184,7 @@ class STTNAutoInpaint:
                                                               lookahead=self.lookahead)                  # bad values: before any frame is read
         feather = seam_feather.refuse_ranks(dist)            # --seam-feather: one process (bad values and several ranks: before any frame is read)
         grain = regrain.refuse_ranks(dist)                   # --regrain: the same
+        flicker = deflicker.refuse_ranks(dist)               # --deflicker: the same
         if (n_context or scene_split or n_ahead) and dist is not None:
             raise RuntimeError("sttn-auto context frames (--sttn-context, --sttn-lookahead) / scene-bounded chunks run in one process: a chunk looks "
                                "back at its predecessor's frames and ahead at its successor's, "
@@ -215,8 +218,8 @@ class STTNAutoInpaint:
         local_areas = [(a[0] - y_lo, a[1] - y_lo, a[2], a[3]) for a in inpaint_area]
         dmask = torch.from_numpy(np.ascontiguousarray(mask[y_lo:y_hi, :, 0])).to(engine.device) if inpaint_area else None
         mask_rows_host = mask[y_lo:y_hi, :, 0] if inpaint_area else None     # the engine reads the rows that hold the mask off this copy
-        # --seam-feather, --regrain: the composite mask of the FULL frame; a loop that hands the engine strip rows says which (STTNInpaint.auto_chunk)
-        cmask = self.sttn_inpaint.composite_mask(mask, thresholded=True) if ((feather or grain) and inpaint_area) else None
+        # --seam-feather, --regrain, --deflicker: the composite mask of the FULL frame; a loop that hands the engine strip rows says which (STTNInpaint.auto_chunk)
+        cmask = self.sttn_inpaint.composite_mask(mask, thresholded=True) if ((feather or grain or flicker) and inpaint_area) else None
         kept = {}
 
         def tick(original, frame):

@@ -296,6 +296,7 @@ class SubtitleRemover:
 
         seam_feather.refuse_ranks(dist)                                                 # --seam-feather: bad values and several ranks, before any frame is read
         seam_feather.regrain.refuse_ranks(dist)                                         # --regrain: the same
+        seam_feather.deflicker.refuse_ranks(dist)                                       # --deflicker: the same
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), propainter_inpaint)
         if single_frame_inpaint is None:
@@ -440,6 +441,7 @@ class SubtitleRemover:
 
         seam_feather.refuse_ranks(self._distributed())                                  # --seam-feather: bad values and several ranks, before any frame is read
         seam_feather.regrain.refuse_ranks(self._distributed())                          # --regrain: the same
+        seam_feather.deflicker.refuse_ranks(self._distributed())                        # --deflicker: the same
         max_load = config.getSttnMaxLoadNum()
         n_context, scene_split, n_ahead = (0, False, 0)
         if getattr(model, "accepts_context", False):
@@ -667,6 +669,7 @@ class SubtitleRemover:
         start_time = time.time()
         seam_feather.refuse_ranks(self._distributed())                   # --seam-feather: a bad value or several ranks fail before any work is done
         seam_feather.regrain.refuse_ranks(self._distributed())           # --regrain: the same
+        seam_feather.deflicker.refuse_ranks(self._distributed())         # --deflicker: the same
         if self._video_writer is None and self.is_path:
             self._y4m_like()                                             # a sink that cannot be made fails before any work is done
         if len(self.sub_areas) == 0:
@@ -723,6 +726,8 @@ def main(argv=None):
         os.environ["VSR_SEAM_FEATHER"] = str(args.seam_feather)
     if args.regrain is not None:
         os.environ["VSR_REGRAIN"] = str(args.regrain)
+    if args.deflicker is not None:
+        os.environ["VSR_DEFLICKER"] = str(args.deflicker)
     sr = SubtitleRemover(args.input)
     sr.sub_areas = [tuple(c) for c in args.subtitle_area_coords]
     if args.output is not None:

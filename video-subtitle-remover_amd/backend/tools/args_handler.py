@@ -43,6 +43,11 @@ def build_parser():
     parser.add_argument("--regrain", type=int, default=None, metavar="P",
                         help="every mode: measure the source's noise in a ring around the inpainted pixels and add P percent of what the "
                              "fill lacks back inside them (100 = match the source, 0 = off, at most 200); one process; sets VSR_REGRAIN")
+    # not in the reference: every mode steadies its fill over time inside the pixels it inpainted (tools/deflicker.py)
+    parser.add_argument("--deflicker", type=int, default=None, metavar="R",
+                        help="every mode: inside the inpainted pixels, mix every frame's fill with the fills of the R frames before and "
+                             "after it in the same batch, as far as the picture around them stood still (0 = off, at most 8); one process; "
+                             "sets VSR_DEFLICKER")
     return parser
 
 
@@ -63,6 +68,13 @@ def parse_args(argv=None):
             regrain_option(args.regrain)
         except ValueError as e:
             parser.error(f"--regrain: {e}")
+    if args.deflicker is not None:
+        from .deflicker import deflicker_option
+
+        try:
+            deflicker_option(args.deflicker)
+        except ValueError as e:
+            parser.error(f"--deflicker: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

@@ -23,6 +23,10 @@ The list form uploads once, runs the device form and downloads once.  Several ra
 
 --regrain P (tools/regrain.py) lives in the same two calls and shares the clone: with P > 0 the fill is regrained between
 steps 3 and 4, out = composite(regrain(fill), src, d, F); with F = 0 and P > 0 steps 1 and 4 fall away.  Both off: the body alone.
+
+--deflicker R (tools/deflicker.py) is a third pass on the same clone, in front of the regrain: body -> deflicker -> regrain
+-> feather, so that regrain measures the smoothed fill's deficit and its fresh per-frame grain is not averaged away.  All off: the body
+alone.
 """
 import collections
 import ctypes as C
@@ -31,7 +35,7 @@ import threading
 
 import numpy as np
 
-from . import regrain
+from . import deflicker, regrain
 
 MAX_FEATHER = 64
 ENV = "VSR_SEAM_FEATHER"
@@ -126,14 +130,18 @@ def composite(frames, src, d, feather):
     return frames
 
 
-def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None):
+def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0):
     """body(frames) inpaints the device tensor `frames` in place (today's call); with F > 0 and a non-empty composite mask the frames
     come back as the definition's.  cmask: the FULL-frame composite mask (host uint8) or a callable that makes it; rows = (y_lo, y_hi):
     `frames` holds these rows of the frame only (sttn-auto's strip rows) -- d is computed on the full frame and sliced, so a mask that
     touches the first or last of the rows ramps as it does in the whole frame.
     grain = P of --regrain (tools/regrain.py), sample_rows = the plugin's (None: the whole frame): with P > 0 the fill is regrained
-    against the same source clone before the composite, out = composite(regrain(fill), src, d, F); with F = 0 regrain alone."""
-    if not (feather or grain) or frames.shape[0] == 0:
+    against the same source clone before the composite, out = composite(regrain(fill), src, d, F); with F = 0 regrain alone.
+    flicker = R of --deflicker (tools/deflicker.py): with R > 0 and more than one frame the fill is steadied over time, against the same
+    clone and in the same sample rows, before the regrain."""
+    if frames.shape[0] < 2:
+        flicker = 0                          # one frame has no neighbour
+    if not (feather or grain or flicker) or frames.shape[0] == 0:
         return body(frames)
     cm = cmask() if callable(cmask) else cmask
     if not cm.any():
@@ -145,9 +153,11 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
         d = alpha(cm, feather, frames.device)
         if rows is not None:
             d = d[rows[0]:rows[1]]
-    sets = regrain.sets(cm, (0, cm.shape[0]) if sample_rows is None else sample_rows, frames.device) if grain else None
+    sets = regrain.sets(cm, (0, cm.shape[0]) if sample_rows is None else sample_rows, frames.device) if (grain or flicker) else None
     src = frames.clone(memory_format=torch.contiguous_format)
     out = body(frames)
+    if flicker:
+        deflicker.apply(frames, src, sets, flicker, y0=0 if rows is None else rows[0])
     if grain:
         regrain.apply(frames, src, sets, grain, y0=0 if rows is None else rows[0])
     if feather:
@@ -163,25 +173,29 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
     kw = {} if context is None else {"context": context}
     if lookahead is not None:
         kw["lookahead"] = lookahead
-    f, g = feather_option(), regrain.regrain_option()
-    if not (f or g):
+    f, g, r = feather_option(), regrain.regrain_option(), deflicker.deflicker_option()
+    if len(input_frames) < 2:
+        r = 0                                # one frame has no neighbour
+    if not (f or g or r):
         return body(input_frames, input_mask, **kw)
     import torch
 
-    sample_rows = plugin.sample_rows(input_mask) if g else None
+    sample_rows = plugin.sample_rows(input_mask) if (g or r) else None
     if isinstance(input_frames, torch.Tensor):
         return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda t: body(t, input_mask, **kw), f,
-                           grain=g, sample_rows=sample_rows)
+                           grain=g, sample_rows=sample_rows, flicker=r)
     if len(input_frames) == 0:
         return body(input_frames, input_mask, **kw)
     cm = plugin.composite_mask(input_mask)
     if not cm.any():
         return body(input_frames, input_mask, **kw)
     if not getattr(plugin, "accepts_device_frames", False):
-        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the regrain and the composite
+        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the three passes
         fill = body(input_frames, input_mask, **kw)
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(fill))).to(device)
         src = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
+        if r:
+            deflicker.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), r)
         if g:
             regrain.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), g)
         if f:
@@ -190,6 +204,6 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
         kw = {name: torch.from_numpy(np.ascontiguousarray(np.stack(c))).to(device)
               for name, c in (("context", context), ("lookahead", lookahead)) if c is not None and len(c)}
-        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f, grain=g, sample_rows=sample_rows)
+        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r)
     out = frames.cpu().numpy()
     return [out[i] for i in range(out.shape[0])]
