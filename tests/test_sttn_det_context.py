@@ -185,7 +185,8 @@ def test_det_context_entry_point_has_no_cpu_path(built_lib, host_engine):
 
 
 def _index_jobs_of_today(start_end, n, mask_of, max_load):
-    """SubtitleRemover.video_inpaint's index_jobs, restated: the job list the options being off must give"""
+    """the walk over frame numbers SubtitleRemover.video_inpaint had of its own before det_jobs became the only one, restated: the job
+    list the options being off must give"""
     from vsr_amd.backend.tools.inpaint_tools import batch_generator
 
     idx, jobs = 0, []

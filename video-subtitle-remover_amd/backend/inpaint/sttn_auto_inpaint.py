@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ..config import config
-from ..tools import deflicker, regrain, seam_feather
+from ..tools import seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask, is_frame_number_in_ab_sections, threshold_mask
 from ..tools.video_io import ArrayWriter, device_bgr_to_planes, device_planes_to_bgr, open_video
 from ...engine import SttnEngine
@@ -88,9 +88,9 @@ class STTNInpaint:
             return self.engine.auto_chunk(frames_dev, mask_dev, areas, **kw)
         y0 = 0 if rows is None else rows[0]
         hull = (y0 + min(a[0] for a in areas), y0 + max(a[1] for a in areas)) if len(areas) else (0, 0)
+        feather, grain, flicker = seam_feather.options()
         return seam_feather.device_call(frames_dev, cmask, lambda t: self.engine.auto_chunk(t, mask_dev, areas, **kw),
-                                        seam_feather.feather_option(), rows=rows, grain=regrain.regrain_option(), sample_rows=hull,
-                                        flicker=deflicker.deflicker_option())
+                                        feather, rows=rows, grain=grain, sample_rows=hull, flicker=flicker)
 
     def __call__(self, input_frames, input_mask):
         mask = threshold_mask(input_mask)
@@ -102,7 +102,7 @@ class STTNInpaint:
         dev = self.engine.device
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(dev, non_blocking=True)
         dmask = torch.from_numpy(np.ascontiguousarray(mask[:, :, 0])).to(dev, non_blocking=True)
-        wanted = seam_feather.feather_option() or regrain.regrain_option() or deflicker.deflicker_option()
+        wanted = any(seam_feather.options())
         cmask = self.composite_mask(mask, thresholded=True) if wanted else None
         self.auto_chunk(frames, dmask, inpaint_area, cmask=cmask, mask_host=mask[:, :, 0])
         out = frames.cpu().numpy()
@@ -182,9 +182,8 @@ class STTNAutoInpaint:
 
         n_context, scene_split, n_ahead = cp.lookback_options(self.context, self.scene_split, self.clip_gap,
                                                               lookahead=self.lookahead)                  # bad values: before any frame is read
-        feather = seam_feather.refuse_ranks(dist)            # --seam-feather: one process (bad values and several ranks: before any frame is read)
-        grain = regrain.refuse_ranks(dist)                   # --regrain: the same
-        flicker = deflicker.refuse_ranks(dist)               # --deflicker: the same
+        # --seam-feather, --regrain, --deflicker: one process (bad values and several ranks: before any frame is read)
+        feather, grain, flicker = seam_feather.refuse_ranks_all(dist)
         if (n_context or scene_split or n_ahead) and dist is not None:
             raise RuntimeError("sttn-auto context frames (--sttn-context, --sttn-lookahead) / scene-bounded chunks run in one process: a chunk looks "
                                "back at its predecessor's frames and ahead at its successor's, "

@@ -18,9 +18,10 @@ import numpy as np
 
 from .config import config
 from .inpaint.sttn_auto_inpaint import STTNAutoInpaint
+from .tools import frame_walk
 from .tools.args_handler import parse_args
 from .tools.constant import InpaintMode
-from .tools.inpaint_tools import batch_generator, create_mask, expand_frame_ranges
+from .tools.inpaint_tools import create_mask, expand_frame_ranges
 from .tools.subtitle_detect import SubtitleDetect
 from .tools.video_io import IMAGE_EXTS, ArrayWriter, AsyncWriter, ffmpeg_path, open_video, open_writer, y4m_out_mode
 
@@ -110,16 +111,12 @@ class SubtitleRemover:
             # over a file that was not (completely) written
             raise sttn_video_inpaint.last_error
 
-    @staticmethod
-    def is_current_frame_no_start(frame_no, continuous_frame_no_list):          # main.py:90-97
-        return any(start_no == frame_no for start_no, _ in continuous_frame_no_list)
+    is_current_frame_no_start = staticmethod(frame_walk.is_current_frame_no_start)     # main.py:90-97
+    find_frame_no_end = staticmethod(frame_walk.find_frame_no_end)                     # main.py:100-107
 
-    @staticmethod
-    def find_frame_no_end(frame_no, continuous_frame_no_list):                   # main.py:100-107
-        for start_no, end_no in continuous_frame_no_list:
-            if start_no <= frame_no <= end_no:
-                return end_no
-        return -1
+    def _device_index(self):
+        dev = self.device
+        return int(dev.split(":")[1]) if isinstance(dev, str) and ":" in dev else 0
 
     def _distributed_rank(self):
         d = self._distributed()
@@ -144,9 +141,10 @@ class SubtitleRemover:
 
         run_batch_parallel(items, process, write, dist=self._distributed(), device=self.device if self._distributed() else "cpu")
 
-    def _open_resident(self):
-        """(ResidentClip, writer planes format) when this run can keep the decoded video in HBM (tools/resident.py: raw planar source
-        and sink, one process, the clip fits), else None: the host-frame loop then runs as before."""
+    def _probe_resident(self, fits, then):
+        """what _open_resident and _open_windowed ask first: one process, no GUI, a file with a raw planar source and sink (the sink is
+        opened here, by the first self.video_writer access), and whether the clip fits VSR_RESIDENT_GB.  When that answer is `fits`
+        -> then(reader, source format, writer format, info), with the reader still open; else None."""
         from .tools.resident import ResidentClip
 
         if self._distributed() is not None or getattr(self, "gui_mode", False) or not self.is_path:
@@ -155,34 +153,36 @@ class SubtitleRemover:
         try:
             fmts = ResidentClip.formats(reader, self.video_writer)
             info = reader.info()
-            if fmts is None or not ResidentClip.fits(info["len"], info["H_ori"], info["W_ori"], fmts[0]["frame_bytes"] if fmts[1].get("keep") else 0):
+            if fmts is None or fits != ResidentClip.fits(info["len"], info["H_ori"], info["W_ori"], fmts[0]["frame_bytes"] if fmts[1].get("keep") else 0):
                 return None
-            t0 = time.time()
-            clip = ResidentClip.load(reader, fmts[0], info["len"], info["H_ori"], info["W_ori"], self.device, keep_planes=bool(fmts[1].get("keep")))
-            self.phase_seconds["read + upload + YUV->BGR"] = time.time() - t0
-            return clip, fmts[1]
+            return then(reader, fmts[0], fmts[1], info)
         finally:
             reader.release()
+
+    def _open_resident(self):
+        """(ResidentClip, writer planes format) when this run can keep the decoded video in HBM (tools/resident.py: raw planar source
+        and sink, one process, the clip fits), else None: the host-frame loop then runs as before."""
+        from .tools.resident import ResidentClip
+
+        def load(reader, fmt, wf, info):
+            t0 = time.time()
+            clip = ResidentClip.load(reader, fmt, info["len"], info["H_ori"], info["W_ori"], self.device, keep_planes=bool(wf.get("keep")))
+            self.phase_seconds["read + upload + YUV->BGR"] = time.time() - t0
+            return clip, wf
+
+        return self._probe_resident(True, load)
 
     def _open_windowed(self):
         """tools/resident_windows.WindowedClip when VSR_IO_RESIDENT=windows (--resident-windows) and this run could keep its video in HBM
         but for the size of the clip; None otherwise (and for a clip that fits: _open_resident took it)"""
         from .tools import resident_windows
-        from .tools.resident import ResidentClip
 
-        if not resident_windows.enabled() or self._distributed() is not None or getattr(self, "gui_mode", False) or not self.is_path:
-            return None
-        reader = open_video(self.video_path)
-        try:
-            fmts = ResidentClip.formats(reader, self.video_writer)
-            info = reader.info()
-            if fmts is None or ResidentClip.fits(info["len"], info["H_ori"], info["W_ori"], fmts[0]["frame_bytes"] if fmts[1].get("keep") else 0):
-                return None
+        def windowed(reader, fmt, wf, info):
             # (the frames a resident clip would hold after loading: a last record cut short is not one of them)
             n = reader.whole_records() if hasattr(reader, "whole_records") else info["len"]
-            return resident_windows.WindowedClip(self.video_path, fmts[0], fmts[1], n, info["H_ori"], info["W_ori"], self.device)
-        finally:
-            reader.release()
+            return resident_windows.WindowedClip(self.video_path, fmt, wf, n, info["H_ori"], info["W_ori"], self.device)
+
+        return self._probe_resident(False, windowed) if resident_windows.enabled() else None
 
     def _windows_do_not_fit(self, why):
         self.append_output(f"resident windows: {why} does not fit half of VSR_RESIDENT_GB; taking the host-frame loop")
@@ -249,6 +249,33 @@ class SubtitleRemover:
             ev.record(torch.cuda.current_stream(dev))
             store.ready(first[j + 1] if j + 1 < len(jobs) else len(clip), ev)
 
+    def _run_resident(self, resident, tbar, plugin, make_jobs, look=None):
+        """the tail of a resident run.  resident: what _open_resident gave; make_jobs(n) -> [(lo, hi, mask)] over the clip's n frames
+        (run inside the "inpainting" phase: propainter's single frames are inpainted on the way): a batch is a slice of the clip,
+        inpainted in place; look(frames): the tools/det_lookback.ResidentLookback of the jobs just made, if any.  The store
+        converts, downloads and writes under the batches (_run_resident_jobs) and is aborted when one fails."""
+        from .tools.resident import StreamingStore
+
+        clip, wf = resident
+
+        def inpaint_all():
+            jobs = [(clip.frames[lo:hi], mask) for lo, hi, mask in make_jobs(len(clip))]
+            self._run_resident_jobs(jobs, plugin, clip, store, look(clip.frames) if look is not None else None)
+
+        store = StreamingStore(clip, self.video_writer, wf, lambda: self.update_progress(tbar, increment=1))
+        try:
+            self._timed("inpainting", inpaint_all)
+        except BaseException:
+            store.abort()
+            raise
+        self._timed("BGR->YUV + download + write (what is left after the last batch)", store.finish)
+
+    def _single_passes_through(self):
+        """propainter_mode without a single-frame plugin: an isolated subtitle frame is written as it is, counted, and warned of once"""
+        self.passed_through_single_frames += 1
+        if self.passed_through_single_frames == 1:
+            self.append_output("warning: no LaMa weights configured (LAMA_MODEL_PATH): isolated subtitle frames pass through")
+
     def _find_subtitles(self, detector, clip, wclip):
         """the detector pass -> (sub_list, wclip): over the resident clip, over the file in windows (pass A; a detector batch that does
         not fit sends the run to the host-frame loop: wclip comes back None), or over host frames"""
@@ -294,9 +321,7 @@ class SubtitleRemover:
         dist = self._distributed()
         from .tools import seam_feather
 
-        seam_feather.refuse_ranks(dist)                                                 # --seam-feather: bad values and several ranks, before any frame is read
-        seam_feather.regrain.refuse_ranks(dist)                                         # --regrain: the same
-        seam_feather.deflicker.refuse_ranks(dist)                                       # --deflicker: the same
+        seam_feather.refuse_ranks_all(dist)          # --seam-feather, --regrain, --deflicker: bad values and several ranks, before any frame is read
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), propainter_inpaint)
         if single_frame_inpaint is None:
@@ -320,109 +345,38 @@ class SubtitleRemover:
             raise Exception(f"No subtitle detected in {self.video_path}")
         ranges = detector.find_continuous_ranges_with_same_mask(sub_list)
         if scene_div_points is None:                 # main.py:165: self.sub_detector.get_scene_div_frame_no(self.video_path)
-            dev = self.device
-            scene_div_points = self._timed("scene cuts", detector.get_scene_div_frame_no, self.video_path,
-                                           device=int(dev.split(":")[1]) if isinstance(dev, str) and ":" in dev else 0,
+            scene_div_points = self._timed("scene cuts", detector.get_scene_div_frame_no, self.video_path, device=self._device_index(),
                                            **self._clip_kw(clip if wclip is None else wclip))
         ranges = detector.split_range_by_scene(ranges, list(scene_div_points))
 
-        def index_jobs(n, single):
-            """the walk of items() below over frame numbers alone -> [(lo, hi, mask)], 0-based, the batches of two frames and more;
-            single(frame, mask): an interval of one frame that LaMa takes"""
-            index, jobs = 0, []
-            while index < n:
-                index += 1
-                if index not in sub_list or not self.is_current_frame_no_start(index, ranges):
-                    continue
-                start_frame_no = index
-                end_frame_no = self.find_frame_no_end(index, ranges)
-                if end_frame_no == -1:
-                    continue
-                index = min(end_frame_no, n)
-                nos = list(range(start_frame_no - 1, index))                          # 0-based indices of the interval
-                mask = create_mask(self.mask_size, sub_list[start_frame_no])
-                for batch in ([nos] if len(nos) == 1 else batch_generator(nos, config.propainterMaxLoadNum.value)):
-                    if len(batch) == 1:
-                        if single_frame_inpaint is None:
-                            self.passed_through_single_frames += 1
-                            if self.passed_through_single_frames == 1:
-                                self.append_output("warning: no LaMa weights configured (LAMA_MODEL_PATH): isolated subtitle frames pass through")
-                        else:
-                            single(batch[0], mask)
-                    else:
-                        jobs.append((batch[0], batch[-1] + 1, mask))
-            return jobs
+        def walk(read):
+            """the one walk of this mode (tools/frame_walk.py), over the reader's frames or over frame numbers"""
+            return frame_walk.propainter_walk(read, sub_list, ranges, lambda start: create_mask(self.mask_size, sub_list[start]),
+                                              config.propainterMaxLoadNum.value)
+
+        def clip_jobs(n, single):
+            """-> [(lo, hi, mask)], 0-based: the batches of a clip of n frames; single(frame, mask): an interval of one frame that LaMa takes"""
+            return frame_walk.clip_jobs(walk(frame_walk.counted(n)), single if single_frame_inpaint is not None else None,
+                                        self._single_passes_through)
 
         if wclip is not None:
             # over the budget: the same batches, on windows of the file that follow each other through HBM (tools/resident_windows.py)
             singles = []
-            jobs = index_jobs(wclip.n, lambda at, mask: singles.append((at, mask)))
+            jobs = clip_jobs(wclip.n, lambda at, mask: singles.append((at, mask)))
             if self._run_windowed(wclip, jobs, propainter_inpaint, tbar, singles, single_frame_inpaint):
                 return
             self.passed_through_single_frames = 0                  # (the host-frame loop below counts them again)
         if resident is not None:
-            # the same walk over frame numbers as items() below, on the clip in HBM: batches are slices inpainted in place
             import torch
-
-            clip, wf = resident
 
             def single(at, mask):                  # main.py:217-224: LamaInpaint.inpaint on the whole frame
                 one = single_frame_inpaint(clip.frames[at].cpu().numpy(), mask)
                 clip.frames[at].copy_(torch.from_numpy(np.ascontiguousarray(one)))
 
-            def inpaint_all():
-                # (slice of the clip, mask): independent batches, run by tools/batch_lanes.py
-                jobs = [(clip.frames[lo:hi], mask) for lo, hi, mask in index_jobs(len(clip), single)]
-                self._run_resident_jobs(jobs, propainter_inpaint, clip, store)
-
-            from .tools.resident import StreamingStore
-
-            store = StreamingStore(clip, self.video_writer, wf, lambda: self.update_progress(tbar, increment=1))
-            try:
-                self._timed("inpainting", inpaint_all)
-            except BaseException:
-                store.abort()
-                raise
-            self._timed("BGR->YUV + download + write (what is left after the last batch)", store.finish)
-            return
+            return self._run_resident(resident, tbar, propainter_inpaint, lambda n: clip_jobs(n, single))
         reader = open_video(self.video_path)
-
-        def items():
-            index = 0
-            while True:
-                ok, frame = reader.read()
-                if not ok:
-                    break
-                index += 1
-                if index not in sub_list:
-                    yield ("pass", frame)
-                    continue
-                if not self.is_current_frame_no_start(index, ranges):
-                    continue
-                start_frame_no = index
-                end_frame_no = self.find_frame_no_end(index, ranges)
-                if end_frame_no == -1:
-                    continue
-                temp_frames = [frame]
-                while index < end_frame_no:
-                    ok, frame = reader.read()
-                    if not ok:
-                        break
-                    index += 1
-                    temp_frames.append(frame)
-                mask = create_mask(self.mask_size, sub_list[start_frame_no])
-                for batch in ([temp_frames] if len(temp_frames) == 1 else batch_generator(temp_frames, config.propainterMaxLoadNum.value)):
-                    if len(batch) == 1:
-                        if single_frame_inpaint is None:
-                            self.passed_through_single_frames += 1
-                            if self.passed_through_single_frames == 1:
-                                self.append_output("warning: no LaMa weights configured (LAMA_MODEL_PATH): isolated subtitle frames pass through")
-                        yield ("pass", single_frame_inpaint(batch[0], mask) if single_frame_inpaint is not None else batch[0])
-                    else:
-                        yield ("work", batch, mask)
-
         try:
-            self._run_items(tbar, items(), propainter_inpaint)
+            self._run_items(tbar, frame_walk.host_items(walk(reader.read), single_frame_inpaint, self._single_passes_through), propainter_inpaint)
         finally:
             reader.release()
 
@@ -439,9 +393,7 @@ class SubtitleRemover:
 
         from .tools import seam_feather
 
-        seam_feather.refuse_ranks(self._distributed())                                  # --seam-feather: bad values and several ranks, before any frame is read
-        seam_feather.regrain.refuse_ranks(self._distributed())                          # --regrain: the same
-        seam_feather.deflicker.refuse_ranks(self._distributed())                        # --deflicker: the same
+        seam_feather.refuse_ranks_all(self._distributed())   # --seam-feather, --regrain, --deflicker: bad values and several ranks, before any frame is read
         max_load = config.getSttnMaxLoadNum()
         n_context, scene_split, n_ahead = (0, False, 0)
         if getattr(model, "accepts_context", False):
@@ -477,9 +429,7 @@ class SubtitleRemover:
         if scene_split:
             # one scene pass (the call propainter_mode makes: the cuts pinned to the reference's SceneManager), over the resident clip
             # when there is one; its numbers are 1-based
-            dev = self.device
-            points = self._timed("scene cuts", detector.get_scene_div_frame_no, self.video_path,
-                                 device=int(dev.split(":")[1]) if isinstance(dev, str) and ":" in dev else 0,
+            points = self._timed("scene cuts", detector.get_scene_div_frame_no, self.video_path, device=self._device_index(),
                                  **self._clip_kw(resident[0] if resident is not None else None))
             cuts = [int(p) - 1 for p in points]
         self.scene_cuts = cuts
@@ -495,50 +445,23 @@ class SubtitleRemover:
                         coords.append(area)
             return create_mask(self.mask_size, coords)
 
-        def index_jobs(n):
-            """the walk of items() below over frame numbers alone -> [(lo, hi, mask)], 0-based: the batches of a clip of n frames"""
-            idx, jobs = 0, []
-            while idx < n:
-                idx += 1
-                if idx not in start_end:
-                    continue
-                first, last = idx, start_end[idx]
-                idx = min(last, n)                                 # frames first .. idx are read (:300-305)
-                mask = interval_mask(first, last)
-                for batch in batch_generator(list(range(first - 1, idx)), config.getSttnMaxLoadNum()):
-                    if len(batch) >= 1:
-                        jobs.append((batch[0], batch[-1] + 1, mask))
-            return jobs
+        det = []
+
+        def clip_jobs(n):
+            """the batches of a clip of n frames -> [(lo, hi, mask)], 0-based: tools/det_lookback.det_jobs, the one walk over frame numbers
+            (options off: no cuts, no context -- the batches this mode has always made); `det` keeps its jobs for ResidentLookback"""
+            det[:] = det_lookback.det_jobs(start_end, n, interval_mask, cuts, n_context, max_load, n_ahead if n_ahead else None)
+            return [(job[0], job[1], job[3]) for job in det]
 
         if wclip is not None:
             # over the budget: the same batches, on windows of the file that follow each other through HBM (tools/resident_windows.py)
-            if self._run_windowed(wclip, index_jobs(wclip.n), model, tbar):
+            if self._run_windowed(wclip, clip_jobs(wclip.n), model, tbar):
                 return
         if resident is not None:
-            # the same walk over frame numbers as items() below, on the clip in HBM: a batch is a slice, inpainted in place
-            clip, wf = resident
-
-            def inpaint_all():
-                if lookback:
-                    # (the source rows a later batch looks back at are copied aside before their batch is inpainted: ResidentLookback)
-                    # (... and the rows a batch looks ahead at, by that batch, before their owners are)
-                    jobs = det_lookback.det_jobs(start_end, len(clip), interval_mask, cuts, n_context, max_load, n_ahead if n_ahead else None)
-                    self._run_resident_jobs([(clip.frames[job[0]:job[1]], job[3]) for job in jobs], model, clip, store,
-                                            det_lookback.ResidentLookback(clip.frames, jobs) if (n_context or n_ahead) else None)
-                    return
-                jobs = [(clip.frames[lo:hi], mask) for lo, hi, mask in index_jobs(len(clip))]
-                self._run_resident_jobs(jobs, model, clip, store)
-
-            from .tools.resident import StreamingStore
-
-            store = StreamingStore(clip, self.video_writer, wf, lambda: self.update_progress(tbar, increment=1))
-            try:
-                self._timed("inpainting", inpaint_all)
-            except BaseException:
-                store.abort()
-                raise
-            self._timed("BGR->YUV + download + write (what is left after the last batch)", store.finish)
-            return
+            # (the source rows a later batch looks back at are copied aside before their batch is inpainted: ResidentLookback)
+            # (... and the rows a batch looks ahead at, by that batch, before their owners are)
+            return self._run_resident(resident, tbar, model, clip_jobs,
+                                      (lambda frames: det_lookback.ResidentLookback(frames, det)) if (n_context or n_ahead) else None)
         reader = open_video(self.video_path)
         process = model
         if n_context or n_ahead:
@@ -575,15 +498,11 @@ class SubtitleRemover:
                     idx += 1
                     frames.append(frame)
                 mask = interval_mask(first, last)
-                if lookback:
-                    for lo, hi, ctx_lo, ahead_hi in det_lookback.piece_jobs(first - 1, first - 1 + len(frames), cuts, n_context, max_load, n_ahead):
-                        if n_context or n_ahead:
-                            n_ctx_of.append((lo - ctx_lo, ahead_hi - hi))
-                        yield ("work", frames[ctx_lo - (first - 1):ahead_hi - (first - 1)], mask)
-                    continue
-                for batch in batch_generator(frames, config.getSttnMaxLoadNum()):
-                    if len(batch) >= 1:
-                        yield ("work", batch, mask)
+                # (options off: no cuts, ctx_lo = lo, ahead_hi = hi -- batch_generator over the interval's frames)
+                for lo, hi, ctx_lo, ahead_hi in det_lookback.piece_jobs(first - 1, first - 1 + len(frames), cuts, n_context, max_load, n_ahead):
+                    if n_context or n_ahead:
+                        n_ctx_of.append((lo - ctx_lo, ahead_hi - hi))
+                    yield ("work", frames[ctx_lo - (first - 1):ahead_hi - (first - 1)], mask)
 
         try:
             self._timed("read + inpainting + write (host frames)", self._run_items, tbar, items(), process)
@@ -660,16 +579,14 @@ class SubtitleRemover:
         if det is None:
             from .tools import ocr_det
 
-            det = ocr_det.from_env(0 if not isinstance(self.device, str) or ":" not in self.device else int(self.device.split(":")[1]))
+            det = ocr_det.from_env(self._device_index())
         return det
 
     def run(self):
         from .tools import seam_feather
 
         start_time = time.time()
-        seam_feather.refuse_ranks(self._distributed())                   # --seam-feather: a bad value or several ranks fail before any work is done
-        seam_feather.regrain.refuse_ranks(self._distributed())           # --regrain: the same
-        seam_feather.deflicker.refuse_ranks(self._distributed())         # --deflicker: the same
+        seam_feather.refuse_ranks_all(self._distributed())   # --seam-feather, --regrain, --deflicker: a bad value or several ranks fail before any work is done
         if self._video_writer is None and self.is_path:
             self._y4m_like()                                             # a sink that cannot be made fails before any work is done
         if len(self.sub_areas) == 0:
@@ -709,25 +626,20 @@ class SubtitleRemover:
         self.append_output(f"Finished in {round(time.time() - start_time)} s")
 
 
+# command-line flags that reach the run through the environment: (attribute of the parsed arguments, variable, value -> string)
+FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDENT", lambda _: "windows"),
+            ("scene_split", "VSR_SCENE_SPLIT", lambda _: "1"), ("sttn_context", "VSR_STTN_CONTEXT", str),
+            ("sttn_lookahead", "VSR_STTN_LOOKAHEAD", str), ("seam_feather", "VSR_SEAM_FEATHER", str), ("regrain", "VSR_REGRAIN", str),
+            ("deflicker", "VSR_DEFLICKER", str))
+
+
 def main(argv=None):
     args = parse_args(argv)
     config.inpaintMode.value = args.inpaint_mode
-    if args.y4m_out is not None:
-        os.environ["VSR_Y4M_OUT"] = args.y4m_out
-    if args.resident_windows:
-        os.environ["VSR_IO_RESIDENT"] = "windows"
-    if args.scene_split:
-        os.environ["VSR_SCENE_SPLIT"] = "1"
-    if args.sttn_context is not None:
-        os.environ["VSR_STTN_CONTEXT"] = str(args.sttn_context)
-    if args.sttn_lookahead is not None:
-        os.environ["VSR_STTN_LOOKAHEAD"] = str(args.sttn_lookahead)
-    if args.seam_feather is not None:
-        os.environ["VSR_SEAM_FEATHER"] = str(args.seam_feather)
-    if args.regrain is not None:
-        os.environ["VSR_REGRAIN"] = str(args.regrain)
-    if args.deflicker is not None:
-        os.environ["VSR_DEFLICKER"] = str(args.deflicker)
+    for attribute, variable, convert in FLAG_ENV:
+        value = getattr(args, attribute)
+        if value is not None and value is not False:
+            os.environ[variable] = convert(value)
     sr = SubtitleRemover(args.input)
     sr.sub_areas = [tuple(c) for c in args.subtitle_area_coords]
     if args.output is not None:

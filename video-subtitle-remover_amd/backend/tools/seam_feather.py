@@ -69,6 +69,16 @@ def refuse_ranks(dist, feather=None):
     return f
 
 
+def options():
+    """-> (F, P, R) of this run: --seam-feather, --regrain and --deflicker as the environment has them (the three passes of one plugin call)"""
+    return feather_option(), regrain.regrain_option(), deflicker.deflicker_option()
+
+
+def refuse_ranks_all(dist):
+    """-> (F, P, R).  The three refusals every entry point makes before any work, in this order: the first bad option wins"""
+    return refuse_ranks(dist), regrain.refuse_ranks(dist), deflicker.refuse_ranks(dist)
+
+
 _alphas = collections.OrderedDict()         # (device index, H, W, F, mask bytes) -> uint8 [H,W] device tensor; least recently used first
 _lock = threading.Lock()
 stats = {"alpha_builds": 0, "alpha_hits": 0, "composites": 0}
@@ -173,7 +183,7 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
     kw = {} if context is None else {"context": context}
     if lookahead is not None:
         kw["lookahead"] = lookahead
-    f, g, r = feather_option(), regrain.regrain_option(), deflicker.deflicker_option()
+    f, g, r = options()
     if len(input_frames) < 2:
         r = 0                                # one frame has no neighbour
     if not (f or g or r):
