@@ -702,6 +702,34 @@ int vsr_deflicker_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t
                         int rows, int c0, int c1, int R, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Tone match (--tone-match S, csrc/tone_kernels.hip; the statement is tests/_tone_statement.py, the design DESIGN.md 4.14): a smooth
+ * offset field that takes the fill's tone step across the mask's seam to zero and fades into the interior, added to the inpainted
+ * pixels.  Stateless; all pointers are device pointers, all work is issued on `stream`, nothing waits for the device.  Frames, rows,
+ * y0 and [c0, c1) are regrain's; S is a percentage of the measured step.  Level-3 cells are the 8 x 8 blocks of the picture, cell
+ * (Y, X) = Y * ceil(W / 8) + X.  Bad arguments (a null pointer, H or W <= 0, H * W * 3 >= 2^31, rows outside the frame, a stride
+ * smaller than a frame, n < 0, S outside 0..100, a cell count outside 0..ceil(H / 8) * ceil(W / 8), a workspace that is not 8-byte
+ * aligned) return VSR_ERR_ARG and launch nothing; n == 0 or S == 0 is success without a launch.
+ * ------------------------------------------------------------------------------------- */
+/* cmask_dev uint8 [H][W] (non-zero: the plugin blends here), sample rows [r0, r1) -> map_dev uint8 [H][W]: bit 0 = E (cmask == 0, a
+ * non-zero within Chebyshev distance 2 inside the frame), bit 1 = M (cmask != 0, a zero within Chebyshev distance 2 inside the frame),
+ * both only where r0 <= y < r1; bit 2 = cmask != 0.  counts_dev: three 64-bit words (zeroed by the call): |E|, |M| and the number of
+ * level-3 cells with a non-zero byte of the map; cells_dev (int32, room for ceil(H / 8) * ceil(W / 8)) lists those cells, in no
+ * particular order. */
+int vsr_tone_sets(const uint8_t* cmask_dev, int H, int W, int r0, int r1, uint8_t* map_dev, uint64_t* counts_dev, int32_t* cells_dev,
+                  void* stream);
+/* bytes of the workspace vsr_tone_apply needs for n frames of an H x W picture (whatever rows they hold); < 0 (VSR_ERR_ARG) for bad
+ * arguments */
+int64_t vsr_tone_workspace_bytes(int H, int W, int n);
+/* IN PLACE on the frames that hold the fill, against the source frames: per frame the sums of src over E and of the fill over M in the
+ * listed cells (ncells of them: counts_dev[2] of vsr_tone_sets, read back by the caller once), the pull to one cell and the push back
+ * down to level 3 in the workspace, then clamp(fill + (S * h + d / 2) / d) (floor, d = 100 * 64 * 256) on the pixels of the mask, h the
+ * bilinear interpolation of the clamped level-3 difference.  A frame with no sample of E or of M in the rows held, or with no pixel of
+ * the mask where frames != src, is left as it is.  The workspace needs no initialisation and holds nothing afterwards. */
+int vsr_tone_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* map_dev,
+                   const int32_t* cells_dev, int ncells, int n, int H, int W, int y0, int rows, int c0, int c1, int S,
+                   void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),
  * with symbolic buffers and the offset tables -- replayed on the CPU by tests/.
  * ------------------------------------------------------------------------------------- */

@@ -48,6 +48,11 @@ def build_parser():
                         help="every mode: inside the inpainted pixels, mix every frame's fill with the fills of the R frames before and "
                              "after it in the same batch, as far as the picture around them stood still (0 = off, at most 8); one process; "
                              "sets VSR_DEFLICKER")
+    # not in the reference: every mode levels its fill's tone to the picture across the seam of the pixels it inpainted (tools/tone_match.py)
+    parser.add_argument("--tone-match", type=int, default=None, metavar="S",
+                        help="every mode: measure the step between the picture just outside the inpainted pixels and the fill just inside "
+                             "them and add S percent of it, faded smoothly into the interior, to the fill (100 = level the seam, 0 = off); "
+                             "one process; sets VSR_TONE_MATCH")
     return parser
 
 
@@ -75,6 +80,13 @@ def parse_args(argv=None):
             deflicker_option(args.deflicker)
         except ValueError as e:
             parser.error(f"--deflicker: {e}")
+    if args.tone_match is not None:
+        from .tone_match import tone_option
+
+        try:
+            tone_option(args.tone_match)
+        except ValueError as e:
+            parser.error(f"--tone-match: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

@@ -27,6 +27,10 @@ steps 3 and 4, out = composite(regrain(fill), src, d, F); with F = 0 and P > 0 s
 --deflicker R (tools/deflicker.py) is a third pass on the same clone, in front of the regrain: body -> deflicker -> regrain
 -> feather, so that regrain measures the smoothed fill's deficit and its fresh per-frame grain is not averaged away.  All off: the body
 alone.
+
+--tone-match S (tools/tone_match.py) is the fourth pass on the same clone and the first to run: body -> tone-match ->
+deflicker -> regrain -> feather.  A levelled fill passes deflicker's gate more often, and regrain's deficit and the feather's ramp see
+the final tone.  All off: the body alone.
 """
 import collections
 import ctypes as C
@@ -35,7 +39,7 @@ import threading
 
 import numpy as np
 
-from . import deflicker, regrain
+from . import deflicker, regrain, tone_match
 
 MAX_FEATHER = 64
 ENV = "VSR_SEAM_FEATHER"
@@ -70,13 +74,14 @@ def refuse_ranks(dist, feather=None):
 
 
 def options():
-    """-> (F, P, R) of this run: --seam-feather, --regrain and --deflicker as the environment has them (the three passes of one plugin call)"""
-    return feather_option(), regrain.regrain_option(), deflicker.deflicker_option()
+    """-> (F, P, R, S) of this run: --seam-feather, --regrain, --deflicker and --tone-match as the environment has them (the four passes
+    of one plugin call)"""
+    return feather_option(), regrain.regrain_option(), deflicker.deflicker_option(), tone_match.tone_option()
 
 
 def refuse_ranks_all(dist):
-    """-> (F, P, R).  The three refusals every entry point makes before any work, in this order: the first bad option wins"""
-    return refuse_ranks(dist), regrain.refuse_ranks(dist), deflicker.refuse_ranks(dist)
+    """-> (F, P, R, S).  The four refusals every entry point makes before any work, in this order: the first bad option wins"""
+    return refuse_ranks(dist), regrain.refuse_ranks(dist), deflicker.refuse_ranks(dist), tone_match.refuse_ranks(dist)
 
 
 _alphas = collections.OrderedDict()         # (device index, H, W, F, mask bytes) -> uint8 [H,W] device tensor; least recently used first
@@ -140,7 +145,7 @@ def composite(frames, src, d, feather):
     return frames
 
 
-def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0):
+def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0, tone=0):
     """body(frames) inpaints the device tensor `frames` in place (today's call); with F > 0 and a non-empty composite mask the frames
     come back as the definition's.  cmask: the FULL-frame composite mask (host uint8) or a callable that makes it; rows = (y_lo, y_hi):
     `frames` holds these rows of the frame only (sttn-auto's strip rows) -- d is computed on the full frame and sliced, so a mask that
@@ -148,10 +153,12 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
     grain = P of --regrain (tools/regrain.py), sample_rows = the plugin's (None: the whole frame): with P > 0 the fill is regrained
     against the same source clone before the composite, out = composite(regrain(fill), src, d, F); with F = 0 regrain alone.
     flicker = R of --deflicker (tools/deflicker.py): with R > 0 and more than one frame the fill is steadied over time, against the same
-    clone and in the same sample rows, before the regrain."""
+    clone and in the same sample rows, before the regrain.
+    tone = S of --tone-match (tools/tone_match.py): with S > 0 the fill's tone is levelled to the source across the seam, against the
+    same clone and in the same sample rows, before everything else."""
     if frames.shape[0] < 2:
         flicker = 0                          # one frame has no neighbour
-    if not (feather or grain or flicker) or frames.shape[0] == 0:
+    if not (feather or grain or flicker or tone) or frames.shape[0] == 0:
         return body(frames)
     cm = cmask() if callable(cmask) else cmask
     if not cm.any():
@@ -163,9 +170,13 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
         d = alpha(cm, feather, frames.device)
         if rows is not None:
             d = d[rows[0]:rows[1]]
-    sets = regrain.sets(cm, (0, cm.shape[0]) if sample_rows is None else sample_rows, frames.device) if (grain or flicker) else None
+    sample_rows = (0, cm.shape[0]) if sample_rows is None else sample_rows
+    sets = regrain.sets(cm, sample_rows, frames.device) if (grain or flicker) else None
+    bands = tone_match.sets(cm, sample_rows, frames.device) if tone else None
     src = frames.clone(memory_format=torch.contiguous_format)
     out = body(frames)
+    if tone:
+        tone_match.apply(frames, src, bands, tone, y0=0 if rows is None else rows[0])
     if flicker:
         deflicker.apply(frames, src, sets, flicker, y0=0 if rows is None else rows[0])
     if grain:
@@ -183,27 +194,29 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
     kw = {} if context is None else {"context": context}
     if lookahead is not None:
         kw["lookahead"] = lookahead
-    f, g, r = options()
+    f, g, r, s = options()
     if len(input_frames) < 2:
         r = 0                                # one frame has no neighbour
-    if not (f or g or r):
+    if not (f or g or r or s):
         return body(input_frames, input_mask, **kw)
     import torch
 
-    sample_rows = plugin.sample_rows(input_mask) if (g or r) else None
+    sample_rows = plugin.sample_rows(input_mask) if (g or r or s) else None
     if isinstance(input_frames, torch.Tensor):
         return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda t: body(t, input_mask, **kw), f,
-                           grain=g, sample_rows=sample_rows, flicker=r)
+                           grain=g, sample_rows=sample_rows, flicker=r, tone=s)
     if len(input_frames) == 0:
         return body(input_frames, input_mask, **kw)
     cm = plugin.composite_mask(input_mask)
     if not cm.any():
         return body(input_frames, input_mask, **kw)
     if not getattr(plugin, "accepts_device_frames", False):
-        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the three passes
+        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the four passes
         fill = body(input_frames, input_mask, **kw)
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(fill))).to(device)
         src = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
+        if s:
+            tone_match.apply(frames, src, tone_match.sets(cm, sample_rows, frames.device), s)
         if r:
             deflicker.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), r)
         if g:
@@ -214,6 +227,6 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
         kw = {name: torch.from_numpy(np.ascontiguousarray(np.stack(c))).to(device)
               for name, c in (("context", context), ("lookahead", lookahead)) if c is not None and len(c)}
-        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r)
+        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r, tone=s)
     out = frames.cpu().numpy()
     return [out[i] for i in range(out.shape[0])]
