@@ -730,6 +730,26 @@ int vsr_tone_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src
                    void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Glyph key (--glyph-key T, csrc/key_kernels.hip; the statement is tests/_key_statement.py, the design DESIGN.md 4.15): where the fill
+ * only repeats the source the source stays bit for bit, where they differ by more than grain the fill goes in, grown by G = 4 pixels
+ * and ramped back to the source over R = 4 more.  Stateless; all pointers are device pointers, all work is issued on `stream`, nothing
+ * waits for the device.  Frames, rows, y0 and [c0, c1) are regrain's; cmask_dev is the composite mask of the whole picture, uint8
+ * [H][W], non-zero = the plugin blends here.  Bad arguments (a null pointer, H or W <= 0, H * W * 3 >= 2^31, rows outside the frame,
+ * c1 < c0, a stride smaller than a frame, n < 0, T outside 1..128, a workspace that is not 8-byte aligned) return VSR_ERR_ARG and
+ * launch nothing; n == 0 or c0 == c1 is success without a launch.
+ * ------------------------------------------------------------------------------------- */
+/* bytes of the workspace vsr_key_apply needs for n frames of an H x W picture (whatever rows they hold): n * H * ceil(W / 64) * 8, a
+ * seed bitmap of 64-bit words with room for a row per picture row; < 0 (VSR_ERR_ARG) for bad arguments */
+int64_t vsr_key_workspace_bytes(int H, int W, int n);
+/* IN PLACE on the frames that hold the fill, against the source frames, two launches: per frame D = max over the channels of
+ * |src - fill| on the pixels of the mask in the rows held, a seed where the 3 x 3 sum of D reaches 9 T, one bit per pixel in the
+ * workspace; then per pixel of the mask a = clamp(8 - e, 0, 4), e the Chebyshev distance to the frame's nearest seed in the rows
+ * held, and (a * fill + (4 - a) * src + 2) / 4 per channel.  Bytes outside the mask, and src, are not written.  The workspace needs
+ * no initialisation and holds nothing afterwards. */
+int vsr_key_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* cmask_dev,
+                  int n, int H, int W, int y0, int rows, int c0, int c1, int T, void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),
  * with symbolic buffers and the offset tables -- replayed on the CPU by tests/.
  * ------------------------------------------------------------------------------------- */

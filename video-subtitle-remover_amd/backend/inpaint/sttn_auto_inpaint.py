@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ..config import config
-from ..tools import seam_feather
+from ..tools import glyph_key, seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask, is_frame_number_in_ab_sections, threshold_mask
 from ..tools.video_io import ArrayWriter, device_bgr_to_planes, device_planes_to_bgr, open_video
 from ...engine import SttnEngine
@@ -80,8 +80,8 @@ class STTNInpaint:
         return (min(a[0] for a in areas), max(a[1] for a in areas)) if areas else (0, 0)
 
     def auto_chunk(self, frames_dev, mask_dev, areas, cmask=None, rows=None, **kw):
-        """SttnEngine.auto_chunk, where all three chunk loops and __call__ end.  cmask: None (--seam-feather, --regrain, --deflicker and
-        --tone-match off: the engine call and nothing else), or the full-frame composite mask; rows = (y_lo, y_hi): frames_dev holds these rows of the frames
+        """SttnEngine.auto_chunk, where all three chunk loops and __call__ end.  cmask: None (--seam-feather, --regrain, --deflicker,
+        --tone-match and --glyph-key off: the engine call and nothing else), or the full-frame composite mask; rows = (y_lo, y_hi): frames_dev holds these rows of the frames
         only, the distance is taken on the full frame and sliced (tools/seam_feather.device_call).  Context frames (kw) are read-only.
         --regrain and --tone-match sample in the hull of `areas`' rows (sample_rows, here from the areas the caller already has)."""
         if cmask is None:
@@ -90,7 +90,8 @@ class STTNInpaint:
         hull = (y0 + min(a[0] for a in areas), y0 + max(a[1] for a in areas)) if len(areas) else (0, 0)
         feather, grain, flicker, tone = seam_feather.options()
         return seam_feather.device_call(frames_dev, cmask, lambda t: self.engine.auto_chunk(t, mask_dev, areas, **kw),
-                                        feather, rows=rows, grain=grain, sample_rows=hull, flicker=flicker, tone=tone)
+                                        feather, rows=rows, grain=grain, sample_rows=hull, flicker=flicker, tone=tone,
+                                        key=glyph_key.key_option())
 
     def __call__(self, input_frames, input_mask):
         mask = threshold_mask(input_mask)
@@ -102,7 +103,7 @@ class STTNInpaint:
         dev = self.engine.device
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(dev, non_blocking=True)
         dmask = torch.from_numpy(np.ascontiguousarray(mask[:, :, 0])).to(dev, non_blocking=True)
-        wanted = any(seam_feather.options())
+        wanted = any(seam_feather.options()) or glyph_key.key_option()
         cmask = self.composite_mask(mask, thresholded=True) if wanted else None
         self.auto_chunk(frames, dmask, inpaint_area, cmask=cmask, mask_host=mask[:, :, 0])
         out = frames.cpu().numpy()
@@ -182,8 +183,9 @@ class STTNAutoInpaint:
 
         n_context, scene_split, n_ahead = cp.lookback_options(self.context, self.scene_split, self.clip_gap,
                                                               lookahead=self.lookahead)                  # bad values: before any frame is read
-        # --seam-feather, --regrain, --deflicker, --tone-match: one process (bad values and several ranks: before any frame is read)
+        # --seam-feather, --regrain, --deflicker, --tone-match, --glyph-key: one process (bad values and several ranks: before any frame is read)
         feather, grain, flicker, tone = seam_feather.refuse_ranks_all(dist)
+        key = glyph_key.key_option()
         if (n_context or scene_split or n_ahead) and dist is not None:
             raise RuntimeError("sttn-auto context frames (--sttn-context, --sttn-lookahead) / scene-bounded chunks run in one process: a chunk looks "
                                "back at its predecessor's frames and ahead at its successor's, "
@@ -217,8 +219,8 @@ class STTNAutoInpaint:
         local_areas = [(a[0] - y_lo, a[1] - y_lo, a[2], a[3]) for a in inpaint_area]
         dmask = torch.from_numpy(np.ascontiguousarray(mask[y_lo:y_hi, :, 0])).to(engine.device) if inpaint_area else None
         mask_rows_host = mask[y_lo:y_hi, :, 0] if inpaint_area else None     # the engine reads the rows that hold the mask off this copy
-        # --seam-feather, --regrain, --deflicker, --tone-match: the composite mask of the FULL frame; a loop that hands the engine strip rows says which (STTNInpaint.auto_chunk)
-        cmask = self.sttn_inpaint.composite_mask(mask, thresholded=True) if ((feather or grain or flicker or tone) and inpaint_area) else None
+        # --seam-feather, --regrain, --deflicker, --tone-match, --glyph-key: the composite mask of the FULL frame; a loop that hands the engine strip rows says which (STTNInpaint.auto_chunk)
+        cmask = self.sttn_inpaint.composite_mask(mask, thresholded=True) if ((feather or grain or flicker or tone or key) and inpaint_area) else None
         kept = {}
 
         def tick(original, frame):

@@ -321,7 +321,7 @@ class SubtitleRemover:
         dist = self._distributed()
         from .tools import seam_feather
 
-        seam_feather.refuse_ranks_all(dist)          # --seam-feather, --regrain, --deflicker, --tone-match: bad values and several ranks, before any frame is read
+        seam_feather.refuse_ranks_all(dist)          # --seam-feather, --regrain, --deflicker, --tone-match, --glyph-key: bad values and several ranks, before any frame is read
         if dist is not None and dist.get_rank() != 0:
             return self._run_items(tbar, (), propainter_inpaint)
         if single_frame_inpaint is None:
@@ -393,7 +393,7 @@ class SubtitleRemover:
 
         from .tools import seam_feather
 
-        seam_feather.refuse_ranks_all(self._distributed())   # --seam-feather, --regrain, --deflicker, --tone-match: bad values and several ranks, before any frame is read
+        seam_feather.refuse_ranks_all(self._distributed())   # --seam-feather, --regrain, --deflicker, --tone-match, --glyph-key: bad values and several ranks, before any frame is read
         max_load = config.getSttnMaxLoadNum()
         n_context, scene_split, n_ahead = (0, False, 0)
         if getattr(model, "accepts_context", False):
@@ -586,7 +586,7 @@ class SubtitleRemover:
         from .tools import seam_feather
 
         start_time = time.time()
-        seam_feather.refuse_ranks_all(self._distributed())   # --seam-feather, --regrain, --deflicker, --tone-match: a bad value or several ranks fail before any work is done
+        seam_feather.refuse_ranks_all(self._distributed())   # --seam-feather, --regrain, --deflicker, --tone-match, --glyph-key: a bad value or several ranks fail before any work is done
         if self._video_writer is None and self.is_path:
             self._y4m_like()                                             # a sink that cannot be made fails before any work is done
         if len(self.sub_areas) == 0:
@@ -630,7 +630,8 @@ class SubtitleRemover:
 FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDENT", lambda _: "windows"),
             ("scene_split", "VSR_SCENE_SPLIT", lambda _: "1"), ("sttn_context", "VSR_STTN_CONTEXT", str),
             ("sttn_lookahead", "VSR_STTN_LOOKAHEAD", str), ("seam_feather", "VSR_SEAM_FEATHER", str), ("regrain", "VSR_REGRAIN", str),
-            ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str))
+            ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str),
+            ("glyph_key", "VSR_GLYPH_KEY", str))
 
 
 def main(argv=None):

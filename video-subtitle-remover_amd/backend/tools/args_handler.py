@@ -53,6 +53,11 @@ def build_parser():
                         help="every mode: measure the step between the picture just outside the inpainted pixels and the fill just inside "
                              "them and add S percent of it, faded smoothly into the interior, to the fill (100 = level the seam, 0 = off); "
                              "one process; sets VSR_TONE_MATCH")
+    # not in the reference: every mode keeps the source wherever its fill only repeats it (tools/glyph_key.py)
+    parser.add_argument("--glyph-key", type=int, default=None, metavar="T",
+                        help="every mode: inside the inpainted pixels, keep the source bit for bit wherever the fill differs from it by "
+                             "less than T levels in the 3x3 mean, and put the fill in only around the pixels where it differs by more, "
+                             "grown by 4 pixels and ramped back over 4 more (0 = off, at most 128); one process; sets VSR_GLYPH_KEY")
     return parser
 
 
@@ -87,6 +92,13 @@ def parse_args(argv=None):
             tone_option(args.tone_match)
         except ValueError as e:
             parser.error(f"--tone-match: {e}")
+    if args.glyph_key is not None:
+        from .glyph_key import key_option
+
+        try:
+            key_option(args.glyph_key)
+        except ValueError as e:
+            parser.error(f"--glyph-key: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

@@ -31,6 +31,12 @@ alone.
 --tone-match S (tools/tone_match.py) is the fourth pass on the same clone and the first to run: body -> tone-match ->
 deflicker -> regrain -> feather.  A levelled fill passes deflicker's gate more often, and regrain's deficit and the feather's ramp see
 the final tone.  All off: the body alone.
+
+--glyph-key T (tools/glyph_key.py) is the fifth pass on the same clone and the last before the feather: body -> tone-match
+-> deflicker -> regrain -> glyph-key -> feather.  It keeps the source wherever the levelled, steadied, regrained fill -- the fill the
+viewer would have seen -- only repeats it, and the feather's ramp at C's edge then works on the keyed frames.  options() and
+refuse_ranks_all() keep naming the first four; T is read through glyph_key.key_option(), and refuse_ranks_all() makes its refusal too.
+All off: the body alone.
 """
 import collections
 import ctypes as C
@@ -39,7 +45,7 @@ import threading
 
 import numpy as np
 
-from . import deflicker, regrain, tone_match
+from . import deflicker, glyph_key, regrain, tone_match
 
 MAX_FEATHER = 64
 ENV = "VSR_SEAM_FEATHER"
@@ -80,8 +86,11 @@ def options():
 
 
 def refuse_ranks_all(dist):
-    """-> (F, P, R, S).  The four refusals every entry point makes before any work, in this order: the first bad option wins"""
-    return refuse_ranks(dist), regrain.refuse_ranks(dist), deflicker.refuse_ranks(dist), tone_match.refuse_ranks(dist)
+    """-> (F, P, R, S).  The refusals every entry point makes before any work, in this order: the first bad option wins.  The fifth,
+    --glyph-key's (tools/glyph_key.py), is made here too; its T is not part of the tuple (glyph_key.key_option() reads it)"""
+    four = refuse_ranks(dist), regrain.refuse_ranks(dist), deflicker.refuse_ranks(dist), tone_match.refuse_ranks(dist)
+    glyph_key.refuse_ranks(dist)
+    return four
 
 
 _alphas = collections.OrderedDict()         # (device index, H, W, F, mask bytes) -> uint8 [H,W] device tensor; least recently used first
@@ -145,7 +154,7 @@ def composite(frames, src, d, feather):
     return frames
 
 
-def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0, tone=0):
+def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0, tone=0, key=0):
     """body(frames) inpaints the device tensor `frames` in place (today's call); with F > 0 and a non-empty composite mask the frames
     come back as the definition's.  cmask: the FULL-frame composite mask (host uint8) or a callable that makes it; rows = (y_lo, y_hi):
     `frames` holds these rows of the frame only (sttn-auto's strip rows) -- d is computed on the full frame and sliced, so a mask that
@@ -155,10 +164,12 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
     flicker = R of --deflicker (tools/deflicker.py): with R > 0 and more than one frame the fill is steadied over time, against the same
     clone and in the same sample rows, before the regrain.
     tone = S of --tone-match (tools/tone_match.py): with S > 0 the fill's tone is levelled to the source across the seam, against the
-    same clone and in the same sample rows, before everything else."""
+    same clone and in the same sample rows, before everything else.
+    key = T of --glyph-key (tools/glyph_key.py): with T > 0 the source is kept, against the same clone, wherever the fill as the other
+    three passes left it only repeats it; the composite follows."""
     if frames.shape[0] < 2:
         flicker = 0                          # one frame has no neighbour
-    if not (feather or grain or flicker or tone) or frames.shape[0] == 0:
+    if not (feather or grain or flicker or tone or key) or frames.shape[0] == 0:
         return body(frames)
     cm = cmask() if callable(cmask) else cmask
     if not cm.any():
@@ -173,6 +184,7 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
     sample_rows = (0, cm.shape[0]) if sample_rows is None else sample_rows
     sets = regrain.sets(cm, sample_rows, frames.device) if (grain or flicker) else None
     bands = tone_match.sets(cm, sample_rows, frames.device) if tone else None
+    keyed = glyph_key.mask(cm, frames.device) if key else None
     src = frames.clone(memory_format=torch.contiguous_format)
     out = body(frames)
     if tone:
@@ -181,6 +193,8 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
         deflicker.apply(frames, src, sets, flicker, y0=0 if rows is None else rows[0])
     if grain:
         regrain.apply(frames, src, sets, grain, y0=0 if rows is None else rows[0])
+    if key:
+        glyph_key.apply(frames, src, keyed, key, y0=0 if rows is None else rows[0])
     if feather:
         composite(frames, src, d, feather)
     return frames if out is None else out
@@ -195,23 +209,24 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
     if lookahead is not None:
         kw["lookahead"] = lookahead
     f, g, r, s = options()
+    t = glyph_key.key_option()
     if len(input_frames) < 2:
         r = 0                                # one frame has no neighbour
-    if not (f or g or r or s):
+    if not (f or g or r or s or t):
         return body(input_frames, input_mask, **kw)
     import torch
 
     sample_rows = plugin.sample_rows(input_mask) if (g or r or s) else None
     if isinstance(input_frames, torch.Tensor):
-        return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda t: body(t, input_mask, **kw), f,
-                           grain=g, sample_rows=sample_rows, flicker=r, tone=s)
+        return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda d: body(d, input_mask, **kw), f,
+                           grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t)
     if len(input_frames) == 0:
         return body(input_frames, input_mask, **kw)
     cm = plugin.composite_mask(input_mask)
     if not cm.any():
         return body(input_frames, input_mask, **kw)
     if not getattr(plugin, "accepts_device_frames", False):
-        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the four passes
+        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the five passes
         fill = body(input_frames, input_mask, **kw)
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(fill))).to(device)
         src = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
@@ -221,12 +236,14 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
             deflicker.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), r)
         if g:
             regrain.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), g)
+        if t:
+            glyph_key.apply(frames, src, glyph_key.mask(cm, frames.device), t)
         if f:
             composite(frames, src, alpha(cm, f, frames.device), f)
     else:
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
         kw = {name: torch.from_numpy(np.ascontiguousarray(np.stack(c))).to(device)
               for name, c in (("context", context), ("lookahead", lookahead)) if c is not None and len(c)}
-        device_call(frames, cm, lambda t: body(t, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r, tone=s)
+        device_call(frames, cm, lambda d: body(d, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t)
     out = frames.cpu().numpy()
     return [out[i] for i in range(out.shape[0])]
