@@ -748,6 +748,17 @@ int64_t vsr_key_workspace_bytes(int H, int W, int n);
  * no initialisation and holds nothing afterwards. */
 int vsr_key_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* cmask_dev,
                   int n, int H, int W, int y0, int rows, int c0, int c1, int T, void* workspace_dev, void* stream);
+/* --glyph-hold K (the statement is tests/_hold_statement.py, the design DESIGN.md 4.16): vsr_key_apply with its seeds held in time.  A
+ * pixel whose 3 x 3 sum of D reaches 9 * ((T + 1) / 2) is a seed too while, within one pixel of it, a frame of the same call among the
+ * K before and the K after is a seed of vsr_key_apply's; nothing is carried from one call to the next.
+ * bytes of the workspace vsr_key_apply_hold needs: 3 * vsr_key_workspace_bytes(H, W, n), three seed bitmaps; < 0 (VSR_ERR_ARG) for bad
+ * arguments */
+int64_t vsr_key_hold_workspace_bytes(int H, int W, int n);
+/* IN PLACE like vsr_key_apply, three launches: the strong and the weak seeds of every frame, the held seeds, the mix.  Every refusal of
+ * vsr_key_apply, and K outside 1..8 (K = 0 is vsr_key_apply), return VSR_ERR_ARG and launch nothing; n == 0 or c0 == c1 is success
+ * without a launch.  The workspace needs no initialisation and holds nothing afterwards. */
+int vsr_key_apply_hold(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* cmask_dev,
+                       int n, int H, int W, int y0, int rows, int c0, int c1, int T, int K, void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),

@@ -631,7 +631,7 @@ FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDE
             ("scene_split", "VSR_SCENE_SPLIT", lambda _: "1"), ("sttn_context", "VSR_STTN_CONTEXT", str),
             ("sttn_lookahead", "VSR_STTN_LOOKAHEAD", str), ("seam_feather", "VSR_SEAM_FEATHER", str), ("regrain", "VSR_REGRAIN", str),
             ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str),
-            ("glyph_key", "VSR_GLYPH_KEY", str))
+            ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str))
 
 
 def main(argv=None):

@@ -58,6 +58,10 @@ def build_parser():
                         help="every mode: inside the inpainted pixels, keep the source bit for bit wherever the fill differs from it by "
                              "less than T levels in the 3x3 mean, and put the fill in only around the pixels where it differs by more, "
                              "grown by 4 pixels and ramped back over 4 more (0 = off, at most 128); one process; sets VSR_GLYPH_KEY")
+    parser.add_argument("--glyph-hold", type=int, default=None, metavar="K",
+                        help="with --glyph-key T: a pixel that differs by at least (T + 1) // 2 levels stays filled while one of the K "
+                             "frames before or after it in the same batch differs by T or more within one pixel of it, so that a glyph "
+                             "that hovers about T does not flicker (0 = off, at most 8); sets VSR_GLYPH_HOLD")
     return parser
 
 
@@ -99,6 +103,14 @@ def parse_args(argv=None):
             key_option(args.glyph_key)
         except ValueError as e:
             parser.error(f"--glyph-key: {e}")
+    if args.glyph_hold is not None:
+        from .glyph_key import hold_option, key_option
+
+        try:
+            if hold_option(args.glyph_hold) and not key_option(args.glyph_key):
+                raise ValueError("it holds the seeds of --glyph-key T, which is off: give both")
+        except ValueError as e:
+            parser.error(f"--glyph-hold: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

@@ -19,6 +19,12 @@ viewer would have seen, and the feather ramps the keyed frames.
     2. vsr_key_apply is launched on the caller's stream with a workspace of vsr_key_workspace_bytes; no word visits the host.
 
 Several ranks are refused (refuse_ranks) before any work, as --tone-match refuses them.
+
+--glyph-hold K (the statement is tests/_hold_statement.py) holds a seed in time: a pixel whose 3 x 3 sum of D reaches
+9 * ((T + 1) // 2) stays a seed while one of the K frames before or after it in the same call has a seed of the plain key within one
+pixel of it.  K = 0 (the default) is the plain key: the same call, launches and bytes.  The option is read here and nowhere else
+(hold_option: --glyph-hold sets VSR_GLYPH_HOLD); K > 0 makes apply() call vsr_key_apply_hold with a workspace of
+vsr_key_hold_workspace_bytes.  K > 0 needs T > 0: refuse_ranks raises otherwise.
 """
 import collections
 import ctypes as C
@@ -29,6 +35,8 @@ import numpy as np
 
 MAX_KEY = 128
 ENV = "VSR_GLYPH_KEY"
+MAX_HOLD = 8
+HOLD_ENV = "VSR_GLYPH_HOLD"
 MAX_MASKS = 4               # masks kept per process: an interval's batches and the lanes present the same mask again and again
 
 
@@ -49,10 +57,31 @@ def key_option(value=None, env=None):
     return t
 
 
-def refuse_ranks(dist, key=None):
+def hold_option(value=None, env=None):
+    """K of this run: `value`, None = the environment (VSR_GLYPH_HOLD, unset or empty = 0 = off).  The one reading of the option.
+    ValueError for anything that is no integer in [0, 8]."""
+    env = os.environ if env is None else env
+    if value is None:
+        value = env.get(HOLD_ENV, "0") or "0"
+    try:
+        k = int(value)
+        if isinstance(value, float) and k != value:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"glyph hold: {value!r} is not an integer") from None
+    if k < 0 or k > MAX_HOLD:
+        raise ValueError(f"glyph hold: K = {k} asked for, 0 <= K <= {MAX_HOLD} are possible (0 = off)")
+    return k
+
+
+def refuse_ranks(dist, key=None, hold=None):
     """-> T.  With T > 0, more than one rank raises before any work: the frames of a call and its source clone live on the rank that
-    runs the call, and the ranks' writers have not been taught the option (the precedent of --regrain)."""
+    runs the call, and the ranks' writers have not been taught the option (the precedent of --regrain).  A bad K, and K > 0 with
+    T = 0 (a hold with no key to hold), raise ValueError here too."""
     t = key_option(key)
+    k = hold_option(hold)
+    if k and not t:
+        raise ValueError(f"--glyph-hold / {HOLD_ENV} = {k} holds the seeds of --glyph-key / {ENV}, which is off: give both or neither")
     if t and dist is not None and dist.get_world_size() > 1:
         raise RuntimeError(f"--glyph-key / {ENV} = {t} runs in one process (world size {dist.get_world_size()}): "
                            "run without it or on one GPU")
@@ -69,7 +98,7 @@ class Mask:
 
 _masks = collections.OrderedDict()          # (device index, H, W, mask bytes) -> Mask; least recently used first
 _lock = threading.Lock()
-stats = {"mask_builds": 0, "mask_hits": 0, "calls": 0}
+stats = {"mask_builds": 0, "mask_hits": 0, "calls": 0, "hold_calls": 0}
 
 
 def mask(cmask, device):
@@ -99,10 +128,11 @@ def mask(cmask, device):
     return m
 
 
-def apply(frames, src, m, T, y0=0):
+def apply(frames, src, m, T, y0=0, hold=None):
     """in place on `frames` (uint8 [n,h,W,3] on the GPU, every frame contiguous; it holds the fill: the rows [y0, y0 + h) of the
     picture) with the source frames `src` (same shape, its own frame stride) under the Mask `m`: vsr_key_apply on the current stream,
-    its seed bitmap in a workspace that lives for the call"""
+    its seed bitmap in a workspace that lives for the call.  hold = K of --glyph-hold, None = hold_option(): with K > 0
+    vsr_key_apply_hold and its three bitmaps instead"""
     import torch
 
     from ..._lib import check, lib
@@ -110,6 +140,7 @@ def apply(frames, src, m, T, y0=0):
     n, h, W, _ = frames.shape
     if n == 0 or not T:
         return frames
+    K = hold_option() if hold is None else int(hold)
     H = m.c.shape[0]
     for t in (frames, src):
         assert t.dtype == torch.uint8 and t.is_cuda and tuple(t.shape) == (n, h, W, 3)
@@ -119,12 +150,18 @@ def apply(frames, src, m, T, y0=0):
     ss = src.stride(0) if n > 1 else h * W * 3
     with torch.cuda.device(frames.device):
         stream = torch.cuda.current_stream(frames.device)
-        nbytes = int(lib.vsr_key_workspace_bytes(H, W, n))
+        nbytes = int(lib.vsr_key_hold_workspace_bytes(H, W, n) if K else lib.vsr_key_workspace_bytes(H, W, n))
         if nbytes < 0:
             check(nbytes)
         work = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.int64, device=frames.device)
         m.c.record_stream(stream)            # (a cached tensor, made on whichever stream asked first)
-        check(lib.vsr_key_apply(C.c_void_p(frames.data_ptr()), fs, C.c_void_p(src.data_ptr()), ss, C.c_void_p(m.c.data_ptr()),
-                                n, H, W, int(y0), h, m.c0, m.c1, int(T), C.c_void_p(work.data_ptr()), C.c_void_p(stream.cuda_stream)))
+        if K:
+            check(lib.vsr_key_apply_hold(C.c_void_p(frames.data_ptr()), fs, C.c_void_p(src.data_ptr()), ss, C.c_void_p(m.c.data_ptr()),
+                                         n, H, W, int(y0), h, m.c0, m.c1, int(T), K, C.c_void_p(work.data_ptr()),
+                                         C.c_void_p(stream.cuda_stream)))
+            stats["hold_calls"] += 1
+        else:
+            check(lib.vsr_key_apply(C.c_void_p(frames.data_ptr()), fs, C.c_void_p(src.data_ptr()), ss, C.c_void_p(m.c.data_ptr()),
+                                    n, H, W, int(y0), h, m.c0, m.c1, int(T), C.c_void_p(work.data_ptr()), C.c_void_p(stream.cuda_stream)))
     stats["calls"] += 1
     return frames

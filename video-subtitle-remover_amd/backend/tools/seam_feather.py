@@ -36,7 +36,7 @@ the final tone.  All off: the body alone.
 -> deflicker -> regrain -> glyph-key -> feather.  It keeps the source wherever the levelled, steadied, regrained fill -- the fill the
 viewer would have seen -- only repeats it, and the feather's ramp at C's edge then works on the keyed frames.  options() and
 refuse_ranks_all() keep naming the first four; T is read through glyph_key.key_option(), and refuse_ranks_all() makes its refusal too.
-All off: the body alone.
+All off: the body alone.  --glyph-hold K lives inside that pass: glyph_key.apply reads it, and is called here as before.
 """
 import collections
 import ctypes as C

@@ -9,4 +9,8 @@ extern "C" {
 // the two per-call launches, in place on the frames; workspace: vsr_key_workspace_bytes(H, W, n) bytes, 8-byte aligned, uninitialised
 int vsr_key_launch(uint8_t* frames, int64_t frame_stride, const uint8_t* src, int64_t src_frame_stride, const uint8_t* cmask, int n, int H, int W,
                    int y0, int rows, int c0, int c1, int T, void* workspace, void* stream);
+// the three per-call launches of --glyph-hold K, 1 <= K <= 8 (checked by vsr_key_apply_hold): the strong and the weak seeds, the seeds
+// held over the K frames to either side, the same mix; workspace: vsr_key_hold_workspace_bytes(H, W, n) bytes, 8-byte aligned, uninitialised
+int vsr_key_hold_launch(uint8_t* frames, int64_t frame_stride, const uint8_t* src, int64_t src_frame_stride, const uint8_t* cmask, int n, int H,
+                        int W, int y0, int rows, int c0, int c1, int T, int K, void* workspace, void* stream);
 }
