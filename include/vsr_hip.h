@@ -292,6 +292,16 @@ int vsr_run_gather_gemm(const GGProblem* probs, int nprobs, int tile_cfg, int bm
  * act carries VSR_ACT_OUT_SPLIT, as plain fp32 otherwise; 6 = variant 5 with the fp16 hi halves alone as
  * operands (fp16 x fp16 -> fp32 accumulate, one MFMA per product); VSR_VARIANT_NARROW: see above */
 int vsr_run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, void* stream);
+/* 7 = variant 4's fp32 tensors (NK or KN) with the operands rounded to fp16 on their way into the matrix cores, one MFMA per product:
+ * the flow engines' fp16 mode (vsr_raft_set_precision mode 2).  Every tile but VSR_TILE_256x128 / VSR_TILE_256x256.
+ * The same launch with the range guard of the reduced-precision variants 4..7 armed: a zeroed device word is passed as the
+ * kernels' range flag and copied to *range_flag_out after the sync.  Bit 0: a stored value left the range of its format
+ * (non-finite, or beyond fp16 under VSR_ACT_OUT_SPLIT) -- what makes an engine redo the chunk in fp32 */
+int vsr_run_gather_gemm_flagged(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, uint32_t* range_flag_out,
+                                void* stream);
+/* workgroups the persistent kernel behind (tile_cfg, bmode, variant 1..7) is launched with at most: CUs x occupancy of that kernel.
+ * A launch of more tiles makes every workgroup take several.  0 for variant 1 (one workgroup per tile); VSR_ERR_NOGPU without a device */
+int vsr_gg_resident_blocks(int tile_cfg, int bmode, int variant);
 int vsr_run_softmax(const SMProblem* probs, int nprobs, void* stream);
 /* fp32 -> split format (variant 5 operands): dst[32c .. 32c+31] as bytes = fp16 hi[0..31] | fp16 lo[0..31] of
  * src[32c .. 32c+31]; n a multiple of 32 */

@@ -51,6 +51,26 @@ def test_no_cpu_fallback(built_lib):
     eng.close()
 
 
+def test_gemm_family_entry_points_without_a_device(built_lib):
+    """the kernel-level additions: argument errors first, then no device -- never a number made up on the host"""
+    import ctypes as C
+
+    lib = built_lib.lib
+    prob, flag = built_lib.GGProblem(), C.c_uint32(7)
+    assert lib.vsr_gg_resident_blocks(built_lib.TILE_128x64, 0, 0) == built_lib.VSR_ERR_ARG
+    assert lib.vsr_gg_resident_blocks(built_lib.TILE_128x64, 0, 8) == built_lib.VSR_ERR_ARG
+    assert lib.vsr_run_gather_gemm_flagged(C.byref(prob), 1, built_lib.TILE_128x64, 0, 3, C.byref(flag), None) == built_lib.VSR_ERR_ARG
+    assert lib.vsr_run_gather_gemm_flagged(C.byref(prob), 1, built_lib.TILE_128x64, 0, 4, None, None) == built_lib.VSR_ERR_ARG
+    assert lib.vsr_run_gather_gemm_variant(C.byref(prob), 1, built_lib.TILE_256x128, 0, 7, None) == built_lib.VSR_ERR_ARG
+    if lib.vsr_device_count() > 0:
+        return
+    assert lib.vsr_gg_resident_blocks(built_lib.TILE_128x64, 0, 3) == built_lib.VSR_ERR_NOGPU
+    assert lib.vsr_gg_resident_blocks(built_lib.TILE_128x64, 0, 1) == built_lib.VSR_ERR_NOGPU
+    assert lib.vsr_run_gather_gemm_variant(C.byref(prob), 1, built_lib.TILE_128x64, 0, 7, None) == built_lib.VSR_ERR_NOGPU
+    assert lib.vsr_run_gather_gemm_flagged(C.byref(prob), 1, built_lib.TILE_128x64, 0, 7, C.byref(flag), None) == built_lib.VSR_ERR_NOGPU
+    assert flag.value == 7
+
+
 def test_strict_state_dict(built_lib):
     from vsr_amd.synth import make_state_dict
     from vsr_amd.engine import SttnEngine

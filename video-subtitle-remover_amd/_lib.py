@@ -110,6 +110,8 @@ SIGNATURES = {
     "vsr_sttn_timing_reset": (_I, [_P]),
     "vsr_run_gather_gemm": (_I, [C.POINTER(GGProblem), _I, _I, _I, _P]),
     "vsr_run_gather_gemm_variant": (_I, [C.POINTER(GGProblem), _I, _I, _I, _I, _P]),
+    "vsr_run_gather_gemm_flagged": (_I, [C.POINTER(GGProblem), _I, _I, _I, _I, C.POINTER(C.c_uint32), _P]),
+    "vsr_gg_resident_blocks": (_I, [_I, _I, _I]),
     "vsr_run_softmax": (_I, [C.POINTER(SMProblem), _I, _P]),
     "vsr_launch_to_split": (_I, [_P, _P, C.c_int64, _P]),
     "vsr_launch_kn_to_nk_split": (_I, [_P, _P, _P, C.c_int, C.c_int, C.c_int64, _P, _P]),

@@ -17,6 +17,9 @@
 extern "C" int vsr_launch_gather_gemm_dev(const GGProblem* d_probs, int nprobs, int totalBlocks, int tileCfg,
                                           int bmode, unsigned int* queue, int variant, int nQueues,
                                           unsigned int* rangeFlag, void* stream);
+// the grid cap of the kernel that (tileCfg, bmode, variant 1..7) selects: CUs x occupancy, the value its launcher clamps the grid to;
+// 0 for variant 1 (one workgroup per tile), < 0 when the combination has no kernel
+extern "C" int vsr_gg_resident_blocks_dev(int tileCfg, int bmode, int variant);
 
 // the 256 x 256 fp16-operand kernel (tile config VSR_TILE_256x256, variant 6, NK; gather_gemm_v7.h): cuts one problem into a body of
 // whole rounds of 256-row tiles and a remainder of short tiles (out: room for 2 problems; returns how many); CUs of the device

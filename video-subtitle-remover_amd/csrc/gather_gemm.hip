@@ -345,15 +345,17 @@ static constexpr int v5_stages(int bm, int bn, int bmode)
 
 template <int BM, int BN, int WM, int WN, int MODE, int ST>
 static void launch_v5_st(const GGProblem* d_probs, int nprobs, int totalBlocks, unsigned int* queue, int nQueues,
-                         unsigned int* rangeFlag, bool hiOnly, hipStream_t stream)
+                         unsigned int* rangeFlag, bool hiOnly, hipStream_t stream, int* ask)
 {
     if (hiOnly) {
         static const int resident = resident_blocks(gather_gemm_f32_v5<BM, BN, WM, WN, MODE, ST, true>);
+        if (ask) { *ask = resident; return; }
         const int g = totalBlocks < resident ? totalBlocks : resident;
         hipLaunchKernelGGL((gather_gemm_f32_v5<BM, BN, WM, WN, MODE, ST, true>), dim3(g), dim3(256), 0, stream, d_probs,
                            nprobs, totalBlocks, queue, nQueues, rangeFlag);
     } else {
         static const int resident = resident_blocks(gather_gemm_f32_v5<BM, BN, WM, WN, MODE, ST, false>);
+        if (ask) { *ask = resident; return; }
         const int g = totalBlocks < resident ? totalBlocks : resident;
         hipLaunchKernelGGL((gather_gemm_f32_v5<BM, BN, WM, WN, MODE, ST, false>), dim3(g), dim3(256), 0, stream, d_probs,
                            nprobs, totalBlocks, queue, nQueues, rangeFlag);
@@ -363,9 +365,10 @@ static void launch_v5_st(const GGProblem* d_probs, int nprobs, int totalBlocks, 
 // runs), VSR_V6_STAGES = 2..4 overrides the stage count.
 template <int BM, int BN, int WM, int WN, int ST>
 static void launch_v6_st(const GGProblem* d_probs, int nprobs, int totalBlocks, unsigned int* queue, int nQueues, unsigned int* rangeFlag,
-                         hipStream_t stream)
+                         hipStream_t stream, int* ask)
 {
     static const int resident = resident_blocks(gather_gemm_f16_v6<BM, BN, WM, WN, ST>, WM * WN * 64);
+    if (ask) { *ask = resident; return; }
     const int g = totalBlocks < resident ? totalBlocks : resident;
     hipLaunchKernelGGL((gather_gemm_f16_v6<BM, BN, WM, WN, ST>), dim3(g), dim3(WM * WN * 64), 0, stream, d_probs, nprobs, totalBlocks, queue, nQueues,
                        rangeFlag);
@@ -413,16 +416,18 @@ extern "C" int vsr_gg_cus(void)
 }
 
 // fp16-operand mode, large NK problems: the 256 x 256 tile of 8 waves, one workgroup per CU (gather_gemm_v7.h)
-static void launch_v7(const GGProblem* d_probs, int nprobs, int totalBlocks, unsigned int* queue, unsigned int* rangeFlag, bool hiOnly, hipStream_t stream)
+static void launch_v7(const GGProblem* d_probs, int nprobs, int totalBlocks, unsigned int* queue, unsigned int* rangeFlag, bool hiOnly, hipStream_t stream, int* ask)
 {
     // tile order: 1 = XCD-aware static slots (default), 0 = first round static, then one atomic counter (VSR_V7_ORDER=0, A/B runs)
     static const int order = [] { const char* e = getenv("VSR_V7_ORDER"); return (e && atoi(e) == 0) ? 0 : 1; }();
     if (hiOnly) {
         static const int resident = resident_blocks(gather_gemm_f16_v7<0>, 512);
+        if (ask) { *ask = resident; return; }
         const int g = totalBlocks < resident ? totalBlocks : resident;
         hipLaunchKernelGGL((gather_gemm_f16_v7<0>), dim3(g), dim3(512), 0, stream, d_probs, nprobs, totalBlocks, queue, rangeFlag, order);
     } else {
         static const int resident = resident_blocks(gather_gemm_f16_v7<1>, 512);
+        if (ask) { *ask = resident; return; }
         const int g = totalBlocks < resident ? totalBlocks : resident;
         hipLaunchKernelGGL((gather_gemm_f16_v7<1>), dim3(g), dim3(512), 0, stream, d_probs, nprobs, totalBlocks, queue, rangeFlag, order);
     }
@@ -430,17 +435,17 @@ static void launch_v7(const GGProblem* d_probs, int nprobs, int totalBlocks, uns
 
 template <int BM, int BN, int WM, int WN, int MODE>
 static void launch_v5(const GGProblem* d_probs, int nprobs, int totalBlocks, unsigned int* queue, int nQueues,
-                      unsigned int* rangeFlag, bool hiOnly, hipStream_t stream)
+                      unsigned int* rangeFlag, bool hiOnly, hipStream_t stream, int* ask)
 {
     if constexpr (MODE == VSR_BMODE_NK && BN >= 64) {
         static const bool useV6 = [] { const char* e = getenv("VSR_F16_KERNEL"); return !(e && atoi(e) == 5); }();
         static const int st6 = [] { const char* e = getenv("VSR_V6_STAGES"); int x = e ? atoi(e) : 0; return (x < 2 || x > 4) ? 3 : x; }();
         if (hiOnly && useV6) {
-            if (st6 == 2) { launch_v6_st<BM, BN, WM, WN, 2>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, stream); return; }
+            if (st6 == 2) { launch_v6_st<BM, BN, WM, WN, 2>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, stream, ask); return; }
             if constexpr ((BM + BN) * 128 * 4 <= 150 * 1024) {
-                if (st6 == 4) { launch_v6_st<BM, BN, WM, WN, 4>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, stream); return; }
+                if (st6 == 4) { launch_v6_st<BM, BN, WM, WN, 4>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, stream, ask); return; }
             }
-            launch_v6_st<BM, BN, WM, WN, 3>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, stream);
+            launch_v6_st<BM, BN, WM, WN, 3>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, stream, ask);
             return;
         }
     }
@@ -449,11 +454,11 @@ static void launch_v5(const GGProblem* d_probs, int nprobs, int totalBlocks, uns
     if constexpr (MODE == VSR_BMODE_NK && BM == 128) {
         // fp16 operands (a third of the MFMA work per byte): the deeper queue pays, 376 vs 360 fps on the bench
         const int st = over ? over : ((hiOnly && BN == 64) ? 3 : v5_stages(BM, BN, MODE));
-        if (st == 2) launch_v5_st<BM, BN, WM, WN, MODE, 2>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream);
-        else if (st == 3) launch_v5_st<BM, BN, WM, WN, MODE, 3>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream);
-        else launch_v5_st<BM, BN, WM, WN, MODE, 4>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream);
+        if (st == 2) launch_v5_st<BM, BN, WM, WN, MODE, 2>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream, ask);
+        else if (st == 3) launch_v5_st<BM, BN, WM, WN, MODE, 3>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream, ask);
+        else launch_v5_st<BM, BN, WM, WN, MODE, 4>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream, ask);
     } else {
-        launch_v5_st<BM, BN, WM, WN, MODE, v5_stages(BM, BN, MODE)>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream);
+        launch_v5_st<BM, BN, WM, WN, MODE, v5_stages(BM, BN, MODE)>(d_probs, nprobs, totalBlocks, queue, nQueues, rangeFlag, hiOnly, stream, ask);
     }
 }
 
@@ -461,23 +466,27 @@ static void launch_v5(const GGProblem* d_probs, int nprobs, int totalBlocks, uns
     do {                                                                                                        \
         if (queue && (variant == 5 || variant == 6)) {                                                          \
             launch_v5<BM, BN, WM, WN, MODE>(d_probs, nprobs, totalBlocks, queue, nQueues == 8 ? 8 : 1, rangeFlag,       \
-                                            variant == 6, stream);                                              \
+                                            variant == 6, stream, ask);                                         \
         } else if (queue && variant == 7) {                                                                     \
             static const int resident = resident_blocks(gather_gemm_f32_v4<BM, BN, WM, WN, MODE, true>);       \
+            if (ask) { *ask = resident; break; }                                                               \
             const int g = totalBlocks < resident ? totalBlocks : resident;                                     \
             hipLaunchKernelGGL((gather_gemm_f32_v4<BM, BN, WM, WN, MODE, true>), dim3(g), block, 0, stream,    \
                                d_probs, nprobs, totalBlocks, queue, nQueues == 8 ? 8 : 1, rangeFlag);          \
         } else if (queue && variant == 4) {                                                                     \
             static const int resident = resident_blocks(gather_gemm_f32_v4<BM, BN, WM, WN, MODE, false>);      \
+            if (ask) { *ask = resident; break; }                                                               \
             const int g = totalBlocks < resident ? totalBlocks : resident;                                     \
             hipLaunchKernelGGL((gather_gemm_f32_v4<BM, BN, WM, WN, MODE, false>), dim3(g), block, 0, stream,   \
                                d_probs, nprobs, totalBlocks, queue, nQueues == 8 ? 8 : 1, rangeFlag);          \
         } else if (queue) {                                                                                     \
             static const int resident = resident_blocks(gather_gemm_f32_v3<BM, BN, WM, WN, MODE>);             \
+            if (ask) { *ask = resident; break; }                                                               \
             const int g = totalBlocks < resident ? totalBlocks : resident;                                     \
             hipLaunchKernelGGL((gather_gemm_f32_v3<BM, BN, WM, WN, MODE>), dim3(g), block, 0, stream, d_probs, \
                                nprobs, totalBlocks, queue, ((nQueues & 0xff) == 8 ? 8 : 1) | (nQueues & 0x100));    \
         } else {                                                                                                \
+            if (ask) { *ask = 0; break; }                                                                       \
             hipLaunchKernelGGL((gather_gemm_f32<BM, BN, WM, WN, MODE>), dim3(totalBlocks), block, 0, stream,   \
                                d_probs, nprobs);                                                               \
         }                                                                                                       \
@@ -493,9 +502,10 @@ static void launch_v5(const GGProblem* d_probs, int nprobs, int totalBlocks, uns
 // through one L2), 1 = a single global queue (many N tiles per row block: spreading them over the XCDs
 // avoids hammering one L2 with the same lines -- measured 101 vs 86 TF on the QKV GEMM).
 // rangeFlag (variants 4, 5, 6): device word that is OR-ed with 1 when an accumulator comes out non-finite.
-extern "C" int vsr_launch_gather_gemm_dev(const GGProblem* d_probs, int nprobs, int totalBlocks, int tileCfg,
-                                          int bmode, unsigned int* queue, int variant, int nQueues,
-                                          unsigned int* rangeFlag, void* stream_)
+// ask (nullable): nothing is launched and *ask receives the grid cap of the persistent kernel that would run -- CUs x occupancy of
+// that instantiation, the `resident` of its launcher; 0 for the one-workgroup-per-tile kernel
+static int gg_dispatch(const GGProblem* d_probs, int nprobs, int totalBlocks, int tileCfg, int bmode, unsigned int* queue, int variant,
+                       int nQueues, unsigned int* rangeFlag, void* stream_, int* ask)
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (totalBlocks <= 0) return 0;
@@ -510,12 +520,12 @@ extern "C" int vsr_launch_gather_gemm_dev(const GGProblem* d_probs, int nprobs, 
     if (variant <= 1) queue = nullptr;
     if (tileCfg == VSR_TILE_256x128) {         // the 8-wave tile of the fp16-operand mode
         if (bmode != VSR_BMODE_NK || variant != 6 || !queue) return -1;
-        launch_v6_st<256, 128, 4, 2, 3>(d_probs, nprobs, totalBlocks, queue, nQueues == 8 ? 8 : 1, rangeFlag, stream);
+        launch_v6_st<256, 128, 4, 2, 3>(d_probs, nprobs, totalBlocks, queue, nQueues == 8 ? 8 : 1, rangeFlag, stream, ask);
         return hipGetLastError() == hipSuccess ? 0 : VSR_ERR_HIP;
     }
     if (tileCfg == VSR_TILE_256x256) {         // the 8-wave 256 x 256 tile of the split-format modes (variant 5: split-half, 6: fp16 operands; dynamic tile height, see gather_gemm_v7.h)
         if (bmode != VSR_BMODE_NK || (variant != 6 && variant != 5) || !queue) return -1;
-        launch_v7(d_probs, nprobs, totalBlocks, queue, rangeFlag, variant == 6, stream);
+        launch_v7(d_probs, nprobs, totalBlocks, queue, rangeFlag, variant == 6, stream, ask);
         return hipGetLastError() == hipSuccess ? 0 : VSR_ERR_HIP;
     }
     if (tileCfg == VSR_TILE_128x128 && bmode == VSR_BMODE_NK) GG_LAUNCH(128, 128, 2, 2, VSR_BMODE_NK);
@@ -527,6 +537,23 @@ extern "C" int vsr_launch_gather_gemm_dev(const GGProblem* d_probs, int nprobs, 
     else
         return -1;
     return hipGetLastError() == hipSuccess ? 0 : VSR_ERR_HIP;
+}
+
+extern "C" int vsr_launch_gather_gemm_dev(const GGProblem* d_probs, int nprobs, int totalBlocks, int tileCfg,
+                                          int bmode, unsigned int* queue, int variant, int nQueues,
+                                          unsigned int* rangeFlag, void* stream_)
+{
+    return gg_dispatch(d_probs, nprobs, totalBlocks, tileCfg, bmode, queue, variant, nQueues, rangeFlag, stream_, nullptr);
+}
+
+// the grid cap of the kernel that (tileCfg, bmode, variant 1..7) selects, as its launcher computes it; < 0: no such kernel
+extern "C" int vsr_gg_resident_blocks_dev(int tileCfg, int bmode, int variant)
+{
+    if (variant < 1 || variant > 7) return -1;
+    unsigned int noQueue = 0;
+    int cap = -1;
+    if (gg_dispatch(nullptr, 1, 1, tileCfg, bmode, &noQueue, variant, 8, nullptr, nullptr, &cap) != 0) return -1;
+    return cap;
 }
 
 // problems of at most four output columns (gather_gemm_narrow.h): NK, tiles of 256 rows (tilesN = 1, splitK = 1), no residual,

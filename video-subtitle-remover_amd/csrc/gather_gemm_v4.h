@@ -366,7 +366,8 @@ gather_gemm_f32_v4(const GGProblem* __restrict__ probs, int nprobs, int totalTil
 #pragma unroll
                     for (int ni = 0; ni < NI; ++ni) {
                         float v = acc[mi][ni][r] * alpha + bv[ni];
-                        nonFinite |= !(__builtin_fabsf(v) <= 3.0e38f);
+                        // (stored values only: the padding rows / columns of a border tile hold whatever their table entries point at)
+                        nonFinite |= (mok && (FULL || nok[ni])) && !(__builtin_fabsf(v) <= 3.0e38f);
                         if (act == VSR_ACT_LRELU02) v = v > 0.f ? v : 0.2f * v;
                         else if (act == VSR_ACT_RELU) v = fmaxf(v, 0.f);
                         else if (act == VSR_ACT_LRELU01) v = v > 0.f ? v : 0.1f * v;

@@ -420,7 +420,8 @@ gather_gemm_f32_v5(const GGProblem* __restrict__ probs, int nprobs, int totalTil
                         else if (act == VSR_ACT_RELU) v = fmaxf(v, 0.f);
                         else if (act == VSR_ACT_LRELU01) v = v > 0.f ? v : 0.1f * v;
                         if constexpr (HASR) { v += rv[r][ni]; if (postRelu) v = fmaxf(v, 0.f); }
-                        nonFinite |= !(__builtin_fabsf(v) <= vmax);      // also catches NaN
+                        // also catches NaN; stored values only (the padding of a border tile holds whatever its table entries point at)
+                        nonFinite |= (mok && (FULL || nok[ni])) && !(__builtin_fabsf(v) <= vmax);
                         if (mok && (FULL || nok[ni])) {
                             if (cSplit) {
                                 typedef _Float16 __attribute__((address_space(1)))* gh;

@@ -425,7 +425,7 @@ gather_gemm_f16_v6(const GGProblem* __restrict__ probs, int nprobs, int totalTil
                             if (ok) { const long long e = 2 * (long long)(rr + cbase[ni]) + cofs; v += (float)((gch)R)[e] + (float)((gch)R)[e + 32]; }
                             if (postRelu) v = fmaxf(v, 0.f);
                         }
-                        nonFinite |= !(__builtin_fabsf(v) <= vmax);
+                        nonFinite |= ok && !(__builtin_fabsf(v) <= vmax);     // stored values only, as gather_gemm_v7.h
                         if constexpr (GG_ABL(32)) { if (v == 12345.678f) C[0] = v; }
                         else if (ok) {
                             if (cSplit) {

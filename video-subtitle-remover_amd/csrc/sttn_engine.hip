@@ -1247,18 +1247,39 @@ static void tile_dims(int cfg, int& BM, int& BN)
     BN = cfg == VSR_TILE_256x256 ? 256 : (cfg == VSR_TILE_128x128 || cfg == VSR_TILE_256x128) ? 128 : ((cfg == VSR_TILE_256x64 || cfg == VSR_TILE_128x64) ? 64 : 32);
 }
 
-static int run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, void* stream_);
+static int run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, uint32_t* range_flag_out, void* stream_);
 
 int vsr_run_gather_gemm(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, void* stream_)
 {
-    return run_gather_gemm_variant(probs, nprobs, tile_cfg, bmode, gg_variant(bmode), stream_);
+    return run_gather_gemm_variant(probs, nprobs, tile_cfg, bmode, gg_variant(bmode), nullptr, stream_);
 }
+
+// variant 7 runs on the tiles every variant serves: the two 8-wave tiles belong to the split-format kernels
+static bool v7_tile_ok(int tile_cfg) { return tile_cfg != VSR_TILE_256x128 && tile_cfg != VSR_TILE_256x256; }
 
 int vsr_run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, void* stream_)
 {
-    if (variant != (1 | VSR_VARIANT_A_EXP) && variant != VSR_VARIANT_NARROW && (variant < 1 || variant > 6))
-        return fail(VSR_ERR_ARG, "kernel variant must be 1..6, VSR_VARIANT_NARROW or 1 | VSR_VARIANT_A_EXP");
-    return run_gather_gemm_variant(probs, nprobs, tile_cfg, bmode, variant, stream_);
+    if (variant != (1 | VSR_VARIANT_A_EXP) && variant != VSR_VARIANT_NARROW && (variant < 1 || variant > 7))
+        return fail(VSR_ERR_ARG, "kernel variant must be 1..7, VSR_VARIANT_NARROW or 1 | VSR_VARIANT_A_EXP");
+    if (variant == 7 && !v7_tile_ok(tile_cfg)) return fail(VSR_ERR_ARG, "kernel variant 7 has no 256x128 / 256x256 tile");
+    return run_gather_gemm_variant(probs, nprobs, tile_cfg, bmode, variant, nullptr, stream_);
+}
+
+int vsr_run_gather_gemm_flagged(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, uint32_t* range_flag_out, void* stream_)
+{
+    if (!range_flag_out) return fail(VSR_ERR_ARG, "bad argument");
+    if (variant < 4 || variant > 7) return fail(VSR_ERR_ARG, "the range guard belongs to kernel variants 4..7");
+    if (variant == 7 && !v7_tile_ok(tile_cfg)) return fail(VSR_ERR_ARG, "kernel variant 7 has no 256x128 / 256x256 tile");
+    return run_gather_gemm_variant(probs, nprobs, tile_cfg, bmode, variant, range_flag_out, stream_);
+}
+
+int vsr_gg_resident_blocks(int tile_cfg, int bmode, int variant)
+{
+    if (variant < 1 || variant > 7) return fail(VSR_ERR_ARG, "kernel variant must be 1..7");
+    if (vsr_device_count() <= 0) return fail(VSR_ERR_NOGPU, "no HIP device; there is no CPU fallback");
+    const int cap = vsr_gg_resident_blocks_dev(tile_cfg, bmode, variant);
+    if (cap < 0) return fail(VSR_ERR_ARG, "no kernel for this tile config / bmode / variant");
+    return cap;
 }
 
 // ---- resident gather-GEMM launch lists (vsr_gemm_plan_*): descriptors and tile queues stay on the device, a run is one
@@ -1329,7 +1350,8 @@ void vsr_gemm_plan_destroy(vsr_gemm_plan_t* p)
     delete p;
 }
 
-static int run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, void* stream_)
+// range_flag_out (nullable, variants 4..7): the launch gets a zeroed device word as its range flag, copied out after the sync
+static int run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, uint32_t* range_flag_out, void* stream_)
 {
     if (!probs || nprobs <= 0) return fail(VSR_ERR_ARG, "bad argument");
     if (vsr_device_count() <= 0) return fail(VSR_ERR_NOGPU, "no HIP device; there is no CPU fallback");
@@ -1352,13 +1374,14 @@ static int run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_
         total += p.tilesM * p.tilesN * p.splitK;
     }
     GGProblem* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, hp.size() * sizeof(GGProblem) + 64));   // + 8 queue counters
+    HIPCHK(hipMalloc((void**)&d, hp.size() * sizeof(GGProblem) + 64));   // + 8 queue counters + the range flag
     HIPCHK(hipMemcpy(d, hp.data(), hp.size() * sizeof(GGProblem), hipMemcpyHostToDevice));
     unsigned int* queue = nullptr;
     if (variant >= 2) {
         queue = (unsigned int*)((char*)d + (hp.size() * sizeof(GGProblem) + 15) / 16 * 16);
-        HIPCHK(hipMemset(queue, 0, 8 * sizeof(unsigned int)));
+        HIPCHK(hipMemset(queue, 0, 9 * sizeof(unsigned int)));
     }
+    unsigned int* rangeFlag = (range_flag_out && queue) ? queue + 8 : nullptr;
     int nQueues = 8;
     for (const auto& p : hp)
         if (p.tilesN > 4) nQueues = gg_wide_queues();
@@ -1378,8 +1401,9 @@ static int run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_
         }
         rc = vsr_launch_gather_gemm_narrow_dev(d, nprobs, total, maxN, maxK, stream);
     } else
-    rc = vsr_launch_gather_gemm_dev(d, nprobs, total, tile_cfg, bmode, queue, variant, nQueues, nullptr, stream);
+    rc = vsr_launch_gather_gemm_dev(d, nprobs, total, tile_cfg, bmode, queue, variant, nQueues, rangeFlag, stream);
     hipError_t e = hipStreamSynchronize(stream);
+    if (rangeFlag && rc == 0 && e == hipSuccess) e = hipMemcpy(range_flag_out, rangeFlag, sizeof(unsigned int), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (rc != 0) return fail(VSR_ERR_HIP, "gather-gemm launch failed (unsupported tile/bmode?)");
     if (e != hipSuccess) return fail(VSR_ERR_HIP, std::string("gather-gemm: ") + hipGetErrorString(e));
