@@ -498,6 +498,7 @@ extern "C" int vsr_launch_reduce_scatter_fmt(const float* part, int nsplit, int6
                                              const int32_t* rowC, const int32_t* colC, float* out, int outSplit,
                                              const float* lsum, int ldL, void* stream)
 {
+    if (N % 4 || (outSplit && N % 32)) return VSR_ERR_ARG;     // four columns per lane, whole 32-chunks in split format
     const int64_t total = (int64_t)M * (N / 4);
     if (total <= 0) return 0;
     hipLaunchKernelGGL(k_reduce_scatter, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, part, nsplit,
@@ -519,6 +520,7 @@ extern "C" int vsr_launch_upsample2x_rows(const float* src, int H, int W, int C,
                                           int nframes, int split, int oyLo, int oyHi, void* stream)
 {
     if (oyLo < 0 || oyHi > 2 * H || oyLo > oyHi) return VSR_ERR_ARG;
+    if (C % 4 || (split && C % 32)) return VSR_ERR_ARG;        // four channels per lane, whole 32-chunks in split format
     const int64_t total = (int64_t)nframes * (oyHi - oyLo) * 2 * W * (C / 4);
     if (total <= 0) return 0;
     hipLaunchKernelGGL(k_upsample2x_nhwc, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, src, H, W, C,
