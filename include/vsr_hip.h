@@ -225,7 +225,10 @@ enum { VSR_ACT_NONE = 0, VSR_ACT_LRELU02 = 1, VSR_ACT_RELU = 2, VSR_ACT_LRELU01 
         * log2(e) into the scores' scale) with rowmax = ((const uint32_t*)bias)[m] in that encoding, and the row sums l[m] =
         * sum_k 2^(..) are taken while the tiles are staged:
         * splitK 1 writes C = (expA . B) / l; splitK > 1 writes the partial planes unnormalised and the partial sums to
-        * ((float*)R)[split * tilesM * BM + m], for vsr_launch_reduce_scatter's caller to divide by their total. */
+        * ((float*)R)[split * tilesM * BM + m], for vsr_launch_reduce_scatter's caller to divide by their total.
+        * The kernel-level entry points below return VSR_ERR_ARG before anything is launched for a ROW_MAX problem outside variant 3 /
+        * NK / splitK 1 or without R, for an A_EXP problem without VSR_VARIANT_A_EXP, without bias (the maxima) or, with splitK > 1,
+        * without R, and for VSR_VARIANT_A_EXP on NK problems or on a tile other than 128x64 / 128x128. */
        VSR_ACT_ROW_MAX = 0x400, VSR_ACT_A_EXP = 0x800 };
 #define VSR_VARIANT_A_EXP 0x100 /* OR-ed into the kernel variant 1 of a KN launch whose problems may carry VSR_ACT_A_EXP */
 #define VSR_VARIANT_NARROW 8    /* problems of at most FOUR output columns (the last conv of a head: RAFT update.py:6-12 flow head conv2,

@@ -1257,6 +1257,29 @@ int vsr_run_gather_gemm(const GGProblem* probs, int nprobs, int tile_cfg, int bm
 // variant 7 runs on the tiles every variant serves: the two 8-wave tiles belong to the split-format kernels
 static bool v7_tile_ok(int tile_cfg) { return tile_cfg != VSR_TILE_256x128 && tile_cfg != VSR_TILE_256x256; }
 
+// The two fused-attention flags re-purpose descriptor fields (ROW_MAX: R is the row-maximum array; A_EXP: bias holds the maxima, R
+// receives the partial row sums) and only the kernels written for them read the fields that way: anywhere else R would be added as
+// a residual through a null rowR, or the raw scores multiplied as they are.  nullptr when the launch is one those kernels serve.
+static const char* fused_attention_misuse(const GGProblem* hp, int nprobs, int tile_cfg, int bmode, int variant)
+{
+    const bool aexpVariant = variant != VSR_VARIANT_NARROW && (variant & VSR_VARIANT_A_EXP) != 0;
+    if (aexpVariant && (bmode != VSR_BMODE_KN || (tile_cfg != VSR_TILE_128x64 && tile_cfg != VSR_TILE_128x128)))
+        return "1 | VSR_VARIANT_A_EXP: KN problems on the 128x64 or the 128x128 tile";
+    for (int i = 0; i < nprobs; ++i) {
+        const GGProblem& p = hp[i];
+        if (p.act & VSR_ACT_ROW_MAX) {
+            if (variant != 3) return "VSR_ACT_ROW_MAX belongs to kernel variant 3";
+            if (bmode != VSR_BMODE_NK || p.splitK > 1 || p.R == nullptr) return "VSR_ACT_ROW_MAX: NK, splitK 1, R = the row-maximum array";
+        }
+        if (p.act & VSR_ACT_A_EXP) {
+            if (!aexpVariant) return "VSR_ACT_A_EXP needs kernel variant 1 | VSR_VARIANT_A_EXP";
+            if (p.bias == nullptr) return "VSR_ACT_A_EXP: bias = the row maxima of the scores";
+            if (p.splitK > 1 && p.R == nullptr) return "VSR_ACT_A_EXP with splitK > 1: R = the partial row sums";
+        }
+    }
+    return nullptr;
+}
+
 int vsr_run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, void* stream_)
 {
     if (variant != (1 | VSR_VARIANT_A_EXP) && variant != VSR_VARIANT_NARROW && (variant < 1 || variant > 7))
@@ -1294,6 +1317,7 @@ int vsr_gemm_plan_create(const GGProblem* probs, int nprobs, int tile_cfg, int b
 {
     if (!probs || nprobs <= 0 || !out) return fail(VSR_ERR_ARG, "bad argument");
     if (variant < 1 || variant > 4) return fail(VSR_ERR_ARG, "kernel variant must be 1..4 (fp32 tensors)");
+    if (const char* why = fused_attention_misuse(probs, nprobs, tile_cfg, bmode, variant)) return fail(VSR_ERR_ARG, why);
     if (vsr_device_count() <= 0) return fail(VSR_ERR_NOGPU, "no HIP device; there is no CPU fallback");
     std::vector<GGProblem> hp(probs, probs + nprobs);
     int BM, BN;
@@ -1354,6 +1378,7 @@ void vsr_gemm_plan_destroy(vsr_gemm_plan_t* p)
 static int run_gather_gemm_variant(const GGProblem* probs, int nprobs, int tile_cfg, int bmode, int variant, uint32_t* range_flag_out, void* stream_)
 {
     if (!probs || nprobs <= 0) return fail(VSR_ERR_ARG, "bad argument");
+    if (const char* why = fused_attention_misuse(probs, nprobs, tile_cfg, bmode, variant)) return fail(VSR_ERR_ARG, why);
     if (vsr_device_count() <= 0) return fail(VSR_ERR_NOGPU, "no HIP device; there is no CPU fallback");
     hipStream_t stream = (hipStream_t)stream_;
     std::vector<GGProblem> hp(probs, probs + nprobs);
