@@ -774,6 +774,28 @@ int vsr_key_apply_hold(uint8_t* frames_dev, int64_t frame_stride, const uint8_t*
                        int n, int H, int W, int y0, int rows, int c0, int c1, int T, int K, void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Static overlays (--logo-scan, csrc/static_kernels.hip; the statement is tests/_static_statement.py, the design DESIGN.md 4.17): the
+ * device part of the pass that finds a station logo or a burnt-in watermark before any frame is inpainted -- an edge pattern that stays
+ * put over the sampled frames of a clip while the picture around it moves.  Integer, bit-exact; all pointers are device pointers, all
+ * work is issued on `stream`, nothing waits for the device.  backend/tools/logo_scan.py labels the grown map with vsr_det_launch_ccl and
+ * chooses the components on the host.  Bad arguments (a null pointer, H or W <= 0, H * W * 3 >= 2^31, a stride smaller than a frame, n
+ * outside 1..65535, ge outside 0..510, first not 0 or 1, need outside 0..65536, mv outside 0..256, grow outside 0..16, a misaligned
+ * plane) return VSR_ERR_ARG and launch nothing.
+ * ------------------------------------------------------------------------------------- */
+/* ONE launch over the n frames frames_dev + idx_dev[k] * frame_stride (uint8 [H][W][3] BGR each; idx_dev int32 [n], every entry a frame
+ * the caller owns): per frame Y = (29 B + 150 G + 77 R + 128) >> 8 and g = |Y[y][x+1] - Y[y][x-1]| + |Y[y+1][x] - Y[y-1][x]| with the
+ * indices clamped to the frame, per pixel lo = min Y, hi = max Y (uint8 [H][W]) and edges = the number of frames with g >= ge (uint16
+ * [H][W], saturating).  first = 1 overwrites the three planes; first = 0 continues them, so the pieces of a clip give what one call
+ * gives.  A workgroup owns a tile of pixels for all n frames; the planes are touched once per call. */
+int vsr_static_accum(const uint8_t* frames_dev, int64_t frame_stride, const int32_t* idx_dev, int n, int H, int W, int ge, int first,
+                     uint8_t* lo_dev, uint8_t* hi_dev, uint16_t* edges_dev, void* stream);
+/* ONE launch on the planes of vsr_static_accum: grown_dev float [H][W] = 1.0 where a pixel with edges >= need lies within `grow` pixels
+ * of Chebyshev distance (pixels outside the frame count as none), else 0.0 -- the map vsr_det_launch_ccl labels at threshold 0.5 --
+ * and moving_dev uint8 [H][W] = 1 where hi - lo >= mv, else 0. */
+int vsr_static_classify(const uint8_t* lo_dev, const uint8_t* hi_dev, const uint16_t* edges_dev, int H, int W, int need, int mv, int grow,
+                        float* grown_dev, uint8_t* moving_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),
  * with symbolic buffers and the offset tables -- replayed on the CPU by tests/.
  * ------------------------------------------------------------------------------------- */

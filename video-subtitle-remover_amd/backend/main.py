@@ -64,6 +64,7 @@ class SubtitleRemover:
         self.isFinished = False
         self.phase_seconds = {}
         self.resident_windows = None             # what a windowed run did (tools/resident_windows.WindowedClip.report); None: no such run
+        self.static_areas = []                   # [(ymin, ymax, xmin, xmax)] that --logo-scan found (tools/logo_scan.py); run() fills it
 
     @property
     def video_writer(self):
@@ -291,6 +292,18 @@ class SubtitleRemover:
                 self._windows_do_not_fit(e)
         return self._timed("detector pass", detector.find_subtitle_frame_no, sub_remover=self, **self._clip_kw(clip)), None
 
+    def _with_static_areas(self, sub_list):
+        """the detector pass's {frame_no: [boxes]} with every area of --logo-scan (self.static_areas) in every frame's list, as
+        (xmin, xmax, ymin, ymax) for the frames 1 .. frame_count; without such areas (the option off) the dictionary as it came"""
+        if not self.static_areas:
+            return sub_list
+        boxes = [(xmin, xmax, ymin, ymax) for ymin, ymax, xmin, xmax in self.static_areas]
+        out = {}
+        for no in range(1, self.frame_count + 1):
+            have = list(sub_list.get(no, []))
+            out[no] = have + [b for b in boxes if b not in have]
+        return out
+
     @staticmethod
     def _clip_kw(clip):
         """the HBM-resident clip is handed on only when there is one: without it the calls keep the reference's signatures"""
@@ -340,6 +353,7 @@ class SubtitleRemover:
         if wclip is not None:
             wclip.want_scene_cuts = scene_div_points is None       # pass A is the one walk over every frame: the scene kernels ride along
         sub_list, wclip = self._find_subtitles(detector, clip, wclip)
+        sub_list = self._with_static_areas(sub_list)     # --logo-scan: a static overlay is in every frame's list
         if len(sub_list) == 0:
             self._run_items(tbar, (), propainter_inpaint)                  # releases the peers before failing
             raise Exception(f"No subtitle detected in {self.video_path}")
@@ -417,6 +431,8 @@ class SubtitleRemover:
         if not lookback:                                           # (with an option on, the answer is in: not a windowed run)
             wclip = self._open_windowed() if on_device and resident is None else None
         sub_list, wclip = self._find_subtitles(detector, resident[0] if resident is not None else None, wclip)
+        sub_list = self._with_static_areas(sub_list)     # --logo-scan: a static overlay is in every frame's list
+        static = [(xmin, xmax, ymin, ymax) for ymin, ymax, xmin, xmax in self.static_areas]
         if len(sub_list) == 0:
             self._run_items(tbar, (), model)
             raise Exception(f"No subtitle detected in {self.video_path}")
@@ -439,8 +455,8 @@ class SubtitleRemover:
             for no in range(first, last):                          # NB: the reference's range excludes `last` (:310)
                 for area in sub_list.get(no, []):
                     xmin, xmax, ymin, ymax = area
-                    if (ymax - ymin) - (xmax - xmin) > config.subtitleYXAxisDifferencePixel.value:
-                        continue                                   # taller than wide: treated as a false detection
+                    if (ymax - ymin) - (xmax - xmin) > config.subtitleYXAxisDifferencePixel.value and area not in static:
+                        continue                                   # taller than wide: treated as a false detection (of text: a static area stays)
                     if area not in coords:
                         coords.append(area)
             return create_mask(self.mask_size, coords)
@@ -587,11 +603,25 @@ class SubtitleRemover:
 
         start_time = time.time()
         seam_feather.refuse_ranks_all(self._distributed())   # --seam-feather, --regrain, --deflicker, --tone-match, --glyph-key: a bad value or several ranks fail before any work is done
+        from .tools import logo_scan
+
+        scan = logo_scan.refuse_ranks(self._distributed())   # --logo-scan: a bad value or several ranks, likewise
         if self._video_writer is None and self.is_path:
             self._y4m_like()                                             # a sink that cannot be made fails before any work is done
+        mode = config.inpaintMode.value
+        if scan:
+            # one pass over the clip before the sink is made: a scan that must fail (a picture, a clip of fewer than 16 frames) leaves no file
+            self.static_areas = self._timed("logo scan", logo_scan.find_areas, self.video_path, device=self._device_index(),
+                                            report=self.append_output)
+            self.append_output(f"logo scan: {len(self.static_areas)} static area{'s' if len(self.static_areas) != 1 else ''} "
+                               f"(ymin, ymax, xmin, xmax): {self.static_areas}")
+            if mode == InpaintMode.STTN_AUTO:
+                # the areas join the boxes of -c; without -c they are the mask, in place of the whole frame
+                if len(self.sub_areas) == 0 and len(self.static_areas) == 0:
+                    raise Exception(f"No static overlay found in {self.video_path} and no subtitle area given (-c)")
+                self.sub_areas.extend(a for a in self.static_areas if a not in self.sub_areas)
         if len(self.sub_areas) == 0:
             self.sub_areas.append((0, self.frame_height, 0, self.frame_width))
-        mode = config.inpaintMode.value
         if self.is_picture:
             self.picture_mode()
         elif mode == InpaintMode.STTN_AUTO:
@@ -631,7 +661,7 @@ FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDE
             ("scene_split", "VSR_SCENE_SPLIT", lambda _: "1"), ("sttn_context", "VSR_STTN_CONTEXT", str),
             ("sttn_lookahead", "VSR_STTN_LOOKAHEAD", str), ("seam_feather", "VSR_SEAM_FEATHER", str), ("regrain", "VSR_REGRAIN", str),
             ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str),
-            ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str))
+            ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str), ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"))
 
 
 def main(argv=None):

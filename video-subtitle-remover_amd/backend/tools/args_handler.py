@@ -62,6 +62,13 @@ def build_parser():
                         help="with --glyph-key T: a pixel that differs by at least (T + 1) // 2 levels stays filled while one of the K "
                              "frames before or after it in the same batch differs by T or more within one pixel of it, so that a glyph "
                              "that hovers about T does not flicker (0 = off, at most 8); sets VSR_GLYPH_HOLD")
+    # not in the reference: every mode finds the static overlays of the clip itself and inpaints them on every frame (tools/logo_scan.py)
+    parser.add_argument("--logo-scan", action="store_true",
+                        help="every mode: one pass over the clip on the GPU first finds the rectangles that hold a static overlay (a "
+                             "station logo, a channel bug, a burnt-in watermark: edges that stay put while the picture around them moves) "
+                             "and inpaints them on every frame; sttn-auto: they join the -c boxes and, without -c, replace the "
+                             "whole-frame default; the other modes: -c keeps restricting the text detector only; finds nothing in a "
+                             "static shot and no overlay larger than a third of the frame; needs 16 frames; one process; sets VSR_LOGO_SCAN=1")
     return parser
 
 
