@@ -774,6 +774,29 @@ int vsr_key_apply_hold(uint8_t* frames_dev, int64_t frame_stride, const uint8_t*
                        int n, int H, int W, int y0, int rows, int c0, int c1, int T, int K, void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Borrow (--borrow B, csrc/borrow_kernels.hip; the statement is tests/_borrow_statement.py, the design DESIGN.md 4.18): where the glyph
+ * key would show fill, and a frame of the same call within B frames shows the real picture at that pixel, that frame's source pixel
+ * goes in instead of the fill -- if the ring around the mask stood still between the two frames and the pixel agrees with the fill to
+ * within deflicker's tolerance.  Stateless; all pointers are device pointers, all work is issued on `stream`, nothing waits for the
+ * device and no word visits the host.  Frames, rows, y0, [c0, c1) and cmask_dev are the glyph key's; counts_dev is vsr_regrain_sets',
+ * stats_dev vsr_regrain_measure's (word 0 per frame is read), pairs_dev vsr_deflicker_pairs' with R = B.  Every refusal of
+ * vsr_key_apply (its T included, 1..128), a null counts_dev, stats_dev or pairs_dev, and B outside 1..8 return VSR_ERR_ARG and launch
+ * nothing; n < 2 or c0 == c1 is success without a launch.
+ * ------------------------------------------------------------------------------------- */
+/* bytes of the workspace vsr_borrow_apply needs: 2 * vsr_key_workspace_bytes(H, W, n), the seed bitmap and the bitmap of the pixels
+ * within 7 of a seed; < 0 (VSR_ERR_ARG) for bad arguments */
+int64_t vsr_borrow_workspace_bytes(int H, int W, int n);
+/* IN PLACE on the frames that hold the fill, three launches: the seeds of vsr_key_apply at T (its kernel); N = the seeds dilated by 7
+ * pixels in both directions among the rows held (the pixels where the key's weight is not 0); then per pixel of the mask with N_t set
+ * the lenders s = t-1, t+1, t-2, t+2, .. t-B, t+B inside [0, n): the first with N_s clear at the pixel and
+ * max_c |src_s - fill_t| < (24 b) >> 4 gives its three source bytes, b = clamp((16 (4 m - X)) / (3 m), 0, 16) the pair's weight
+ * (deflicker's without its "changed" rule: m = 3 |E|, X = max(0, pairs - ((15447 (A_t + A_s)) >> 17))); with none the fill stays.
+ * Bytes outside the mask, and src, are not written.  The workspace needs no initialisation and holds nothing afterwards. */
+int vsr_borrow_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* cmask_dev,
+                     const uint64_t* counts_dev, const uint64_t* stats_dev, const uint64_t* pairs_dev, int n, int H, int W, int y0, int rows,
+                     int c0, int c1, int T, int B, void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Static overlays (--logo-scan, csrc/static_kernels.hip; the statement is tests/_static_statement.py, the design DESIGN.md 4.17): the
  * device part of the pass that finds a station logo or a burnt-in watermark before any frame is inpainted -- an edge pattern that stays
  * put over the sampled frames of a clip while the picture around it moves.  Integer, bit-exact; all pointers are device pointers, all

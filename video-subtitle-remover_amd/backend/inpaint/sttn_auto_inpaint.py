@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ..config import config
-from ..tools import glyph_key, seam_feather
+from ..tools import borrow, glyph_key, seam_feather
 from ..tools.inpaint_tools import get_inpaint_area_by_mask, is_frame_number_in_ab_sections, threshold_mask
 from ..tools.video_io import ArrayWriter, device_bgr_to_planes, device_planes_to_bgr, open_video
 from ...engine import SttnEngine
@@ -89,9 +89,11 @@ class STTNInpaint:
         y0 = 0 if rows is None else rows[0]
         hull = (y0 + min(a[0] for a in areas), y0 + max(a[1] for a in areas)) if len(areas) else (0, 0)
         feather, grain, flicker, tone = seam_feather.options()
+        key = glyph_key.key_option()
+        lend = borrow.borrow_option() if key else 0
         return seam_feather.device_call(frames_dev, cmask, lambda t: self.engine.auto_chunk(t, mask_dev, areas, **kw),
                                         feather, rows=rows, grain=grain, sample_rows=hull, flicker=flicker, tone=tone,
-                                        key=glyph_key.key_option())
+                                        key=key, borrow=lend)
 
     def __call__(self, input_frames, input_mask):
         mask = threshold_mask(input_mask)

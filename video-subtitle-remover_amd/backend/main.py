@@ -661,7 +661,8 @@ FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDE
             ("scene_split", "VSR_SCENE_SPLIT", lambda _: "1"), ("sttn_context", "VSR_STTN_CONTEXT", str),
             ("sttn_lookahead", "VSR_STTN_LOOKAHEAD", str), ("seam_feather", "VSR_SEAM_FEATHER", str), ("regrain", "VSR_REGRAIN", str),
             ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str),
-            ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str), ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"))
+            ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str), ("borrow", "VSR_BORROW", str),
+            ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"))
 
 
 def main(argv=None):

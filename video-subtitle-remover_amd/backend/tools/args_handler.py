@@ -62,6 +62,12 @@ def build_parser():
                         help="with --glyph-key T: a pixel that differs by at least (T + 1) // 2 levels stays filled while one of the K "
                              "frames before or after it in the same batch differs by T or more within one pixel of it, so that a glyph "
                              "that hovers about T does not flicker (0 = off, at most 8); sets VSR_GLYPH_HOLD")
+    # not in the reference: every mode fills from the real picture of neighbouring frames where it can (tools/borrow.py)
+    parser.add_argument("--borrow", type=int, default=None, metavar="B",
+                        help="with --glyph-key T: where the key would show fill and one of the B frames before or after in the same batch "
+                             "shows the real picture at that pixel, take that frame's pixel instead of the fill, if the picture around the "
+                             "inpainted pixels stood still between the two and the pixel lies within 24 levels of the fill (0 = off, at "
+                             "most 8); sets VSR_BORROW")
     # not in the reference: every mode finds the static overlays of the clip itself and inpaints them on every frame (tools/logo_scan.py)
     parser.add_argument("--logo-scan", action="store_true",
                         help="every mode: one pass over the clip on the GPU first finds the rectangles that hold a static overlay (a "
@@ -118,6 +124,15 @@ def parse_args(argv=None):
                 raise ValueError("it holds the seeds of --glyph-key T, which is off: give both")
         except ValueError as e:
             parser.error(f"--glyph-hold: {e}")
+    if args.borrow is not None:
+        from .borrow import borrow_option
+        from .glyph_key import key_option
+
+        try:
+            if borrow_option(args.borrow) and not key_option(args.glyph_key):
+                raise ValueError("it borrows where --glyph-key T would show fill, and that is off: give both")
+        except ValueError as e:
+            parser.error(f"--borrow: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

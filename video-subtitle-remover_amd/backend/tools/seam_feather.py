@@ -37,6 +37,12 @@ the final tone.  All off: the body alone.
 viewer would have seen -- only repeats it, and the feather's ramp at C's edge then works on the keyed frames.  options() and
 refuse_ranks_all() keep naming the first four; T is read through glyph_key.key_option(), and refuse_ranks_all() makes its refusal too.
 All off: the body alone.  --glyph-hold K lives inside that pass: glyph_key.apply reads it, and is called here as before.
+
+--borrow B (tools/borrow.py) is the sixth pass on the same clone, between the regrain and the key: body -> tone-match ->
+deflicker -> regrain -> borrow -> glyph-key -> feather.  A borrowed pixel is real picture, so the three passes that level, mix and
+regrain the model's fill run before it and do not touch it; the key then judges the frames as the borrow left them.  It needs T > 0 and
+the plugin's sample rows (the ring of --regrain gates it); B is read through borrow.borrow_option(), and refuse_ranks_all() makes its
+refusals too.  B = 0: the calls above and nothing else.
 """
 import collections
 import ctypes as C
@@ -45,6 +51,7 @@ import threading
 
 import numpy as np
 
+from . import borrow as borrow_pass
 from . import deflicker, glyph_key, regrain, tone_match
 
 MAX_FEATHER = 64
@@ -87,9 +94,11 @@ def options():
 
 def refuse_ranks_all(dist):
     """-> (F, P, R, S).  The refusals every entry point makes before any work, in this order: the first bad option wins.  The fifth,
-    --glyph-key's (tools/glyph_key.py), is made here too; its T is not part of the tuple (glyph_key.key_option() reads it)"""
+    --glyph-key's (tools/glyph_key.py), is made here too; its T is not part of the tuple (glyph_key.key_option() reads it), and
+    --borrow's (tools/borrow.py) after it"""
     four = refuse_ranks(dist), regrain.refuse_ranks(dist), deflicker.refuse_ranks(dist), tone_match.refuse_ranks(dist)
     glyph_key.refuse_ranks(dist)
+    borrow_pass.refuse_ranks(dist)
     return four
 
 
@@ -154,7 +163,7 @@ def composite(frames, src, d, feather):
     return frames
 
 
-def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0, tone=0, key=0):
+def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0, tone=0, key=0, borrow=0):
     """body(frames) inpaints the device tensor `frames` in place (today's call); with F > 0 and a non-empty composite mask the frames
     come back as the definition's.  cmask: the FULL-frame composite mask (host uint8) or a callable that makes it; rows = (y_lo, y_hi):
     `frames` holds these rows of the frame only (sttn-auto's strip rows) -- d is computed on the full frame and sliced, so a mask that
@@ -166,9 +175,13 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
     tone = S of --tone-match (tools/tone_match.py): with S > 0 the fill's tone is levelled to the source across the seam, against the
     same clone and in the same sample rows, before everything else.
     key = T of --glyph-key (tools/glyph_key.py): with T > 0 the source is kept, against the same clone, wherever the fill as the other
-    three passes left it only repeats it; the composite follows."""
+    three passes left it only repeats it; the composite follows.
+    borrow = B of --borrow (tools/borrow.py): with B > 0, T > 0 and more than one frame, a pixel the key would show fill at takes the
+    source pixel of a frame of the call within B frames that shows the real picture there, in front of the key."""
     if frames.shape[0] < 2:
         flicker = 0                          # one frame has no neighbour
+    if frames.shape[0] < 2 or not key:
+        borrow = 0
     if not (feather or grain or flicker or tone or key) or frames.shape[0] == 0:
         return body(frames)
     cm = cmask() if callable(cmask) else cmask
@@ -182,7 +195,7 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
         if rows is not None:
             d = d[rows[0]:rows[1]]
     sample_rows = (0, cm.shape[0]) if sample_rows is None else sample_rows
-    sets = regrain.sets(cm, sample_rows, frames.device) if (grain or flicker) else None
+    sets = regrain.sets(cm, sample_rows, frames.device) if (grain or flicker or borrow) else None
     bands = tone_match.sets(cm, sample_rows, frames.device) if tone else None
     keyed = glyph_key.mask(cm, frames.device) if key else None
     src = frames.clone(memory_format=torch.contiguous_format)
@@ -193,6 +206,8 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
         deflicker.apply(frames, src, sets, flicker, y0=0 if rows is None else rows[0])
     if grain:
         regrain.apply(frames, src, sets, grain, y0=0 if rows is None else rows[0])
+    if borrow:
+        borrow_pass.apply(frames, src, sets, keyed, key, borrow, y0=0 if rows is None else rows[0])
     if key:
         glyph_key.apply(frames, src, keyed, key, y0=0 if rows is None else rows[0])
     if feather:
@@ -210,23 +225,24 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
         kw["lookahead"] = lookahead
     f, g, r, s = options()
     t = glyph_key.key_option()
+    b = borrow_pass.borrow_option() if t else 0
     if len(input_frames) < 2:
-        r = 0                                # one frame has no neighbour
+        r = b = 0                            # one frame has no neighbour
     if not (f or g or r or s or t):
         return body(input_frames, input_mask, **kw)
     import torch
 
-    sample_rows = plugin.sample_rows(input_mask) if (g or r or s) else None
+    sample_rows = plugin.sample_rows(input_mask) if (g or r or s or b) else None
     if isinstance(input_frames, torch.Tensor):
         return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda d: body(d, input_mask, **kw), f,
-                           grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t)
+                           grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t, borrow=b)
     if len(input_frames) == 0:
         return body(input_frames, input_mask, **kw)
     cm = plugin.composite_mask(input_mask)
     if not cm.any():
         return body(input_frames, input_mask, **kw)
     if not getattr(plugin, "accepts_device_frames", False):
-        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the five passes
+        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the six passes
         fill = body(input_frames, input_mask, **kw)
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(fill))).to(device)
         src = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
@@ -236,6 +252,8 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
             deflicker.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), r)
         if g:
             regrain.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), g)
+        if b:
+            borrow_pass.apply(frames, src, regrain.sets(cm, sample_rows, frames.device), glyph_key.mask(cm, frames.device), t, b)
         if t:
             glyph_key.apply(frames, src, glyph_key.mask(cm, frames.device), t)
         if f:
@@ -244,6 +262,7 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
         kw = {name: torch.from_numpy(np.ascontiguousarray(np.stack(c))).to(device)
               for name, c in (("context", context), ("lookahead", lookahead)) if c is not None and len(c)}
-        device_call(frames, cm, lambda d: body(d, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t)
+        device_call(frames, cm, lambda d: body(d, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t,
+                    borrow=b)
     out = frames.cpu().numpy()
     return [out[i] for i in range(out.shape[0])]

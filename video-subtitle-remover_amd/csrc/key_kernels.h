@@ -13,4 +13,8 @@ int vsr_key_launch(uint8_t* frames, int64_t frame_stride, const uint8_t* src, in
 // held over the K frames to either side, the same mix; workspace: vsr_key_hold_workspace_bytes(H, W, n) bytes, 8-byte aligned, uninitialised
 int vsr_key_hold_launch(uint8_t* frames, int64_t frame_stride, const uint8_t* src, int64_t src_frame_stride, const uint8_t* cmask, int n, int H,
                         int W, int y0, int rows, int c0, int c1, int T, int K, void* workspace, void* stream);
+// the seed launch of vsr_key_launch alone (--borrow, borrow_kernels.hip): [sa, sb) are the bitmap's rows as rows of the frames (the
+// rows [c0 - 1, c1 + 1) of the picture that the frames hold, not empty); bitmap: n * (sb - sa) * ceil(W / 64) words, every one written
+int vsr_key_seeds_launch(const uint8_t* frames, int64_t frame_stride, const uint8_t* src, int64_t src_frame_stride, const uint8_t* cmask, int n,
+                         int W, int y0, int rows, int sa, int sb, int T, void* bitmap, void* stream);
 }

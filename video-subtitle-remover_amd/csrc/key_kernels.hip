@@ -228,6 +228,18 @@ extern "C" int vsr_key_launch(uint8_t* frames, int64_t frame_stride, const uint8
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// k_key_seeds alone, for --borrow (borrow_kernels.hip): the bitmap [n][sb - sa][nw] of the rows [sa, sb) of the frames, every word written
+extern "C" int vsr_key_seeds_launch(const uint8_t* frames, int64_t frame_stride, const uint8_t* src, int64_t src_frame_stride,
+                                    const uint8_t* cmask, int n, int W, int y0, int rows, int sa, int sb, int T, void* bitmap, void* stream)
+{
+    const int nw = (W + 63) / 64;
+    const unsigned gz = (unsigned)(n < KY_MAX_GZ ? n : KY_MAX_GZ);
+    hipLaunchKernelGGL(k_key_seeds, dim3((unsigned)nw, (unsigned)((sb - sa + KY_TILE - 1) / KY_TILE), gz), dim3(KY_THREADS), 0,
+                       (hipStream_t)stream, frames, frame_stride, src, src_frame_stride, cmask, n, W, y0, rows, sa, sb, nw, 9 * T,
+                       (unsigned long long*)bitmap);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // three launches: the strong and the weak seeds, the held seeds, k_key_apply on the held seeds.  The workspace holds the three bitmaps
 // [n][sb - sa][nw] one behind the other
 extern "C" int vsr_key_hold_launch(uint8_t* frames, int64_t frame_stride, const uint8_t* src, int64_t src_frame_stride, const uint8_t* cmask, int n,
