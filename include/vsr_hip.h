@@ -797,6 +797,34 @@ int vsr_borrow_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* s
                      int c0, int c1, int T, int B, void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Borrow along a pan (--borrow-pan P, csrc/borrow_pan_kernels.hip; the statement is tests/_borrow_pan_statement.py, the design DESIGN.md
+ * 4.19): --borrow with a rigid integer shift per pair of frames, found by a block-matching search over the ring E.  Stateless; all
+ * pointers are device pointers, all work is issued on `stream`, nothing waits for the device and no word visits the host.  Frames,
+ * rows, y0, [c0, c1), cmask_dev, counts_dev and stats_dev are vsr_borrow_apply's; map_dev is vsr_regrain_sets' map.  Every refusal of
+ * vsr_borrow_apply, and P outside 1..8 (P = 0 is vsr_borrow_apply), return VSR_ERR_ARG and launch nothing; n < 2 or c0 == c1 is
+ * success without a launch.
+ * The workspace, 8-byte aligned, in 64-bit words: the table [n][B][NC + 1][2], NC = max((2 P + 1)^2, 10), slot i of the pair (t, t + k)
+ * holding (S, cnt) of its shift -- k = 1: (dy, dx) = (i / (2 P + 1) - P, i % (2 P + 1) - P); k >= 2: slot 9 is (0, 0), slots 0..8 are
+ * the level's centre + (i / 3 - 1, i % 3 - 1), left 0 where that is (0, 0) or beyond k P; the pair behind the slots is the kernels'
+ * own -- then n * B words of chosen shifts, then vsr_borrow_apply's two bitmaps.
+ * ------------------------------------------------------------------------------------- */
+/* bytes of that workspace; < 0 (VSR_ERR_ARG) for bad arguments */
+int64_t vsr_borrow_pan_workspace_bytes(int H, int W, int n, int B, int P);
+/* clears the table and fills it, one launch per level k = 1 .. min(B, n - 1): level 1 tries every shift within P, level k the nine
+ * shifts around (the best of level k - 1 of frame t) + (the best of level 1 of frame t + k - 1) and (0, 0).  The workspace needs no
+ * initialisation. */
+int vsr_borrow_pan_search(const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* map_dev, const uint64_t* counts_dev, int n, int H,
+                          int W, int y0, int rows, int c0, int c1, int B, int P, void* workspace_dev, void* stream);
+/* IN PLACE on the frames that hold the fill, on the workspace vsr_borrow_pan_search left, four launches: the seeds and N of
+ * vsr_borrow_apply, the chosen shift D and weight w of every pair from the table, then per pixel p of the mask with N_t set the lenders
+ * in vsr_borrow_apply's order, s = t + k read at q = p + D(t, k), s = t - k at q = p - D(s, k): the first with q inside the rows held,
+ * cmask[q] == 0 or N_s clear at q, and max_c |src_s[q] - fill_t[p]| < (24 w) >> 4 gives its three source bytes.  Bytes outside the mask,
+ * and src, are not written. */
+int vsr_borrow_pan_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_frame_stride, const uint8_t* cmask_dev,
+                         const uint64_t* counts_dev, const uint64_t* stats_dev, int n, int H, int W, int y0, int rows, int c0, int c1, int T,
+                         int B, int P, void* workspace_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Static overlays (--logo-scan, csrc/static_kernels.hip; the statement is tests/_static_statement.py, the design DESIGN.md 4.17): the
  * device part of the pass that finds a station logo or a burnt-in watermark before any frame is inpainted -- an edge pattern that stays
  * put over the sampled frames of a clip while the picture around it moves.  Integer, bit-exact; all pointers are device pointers, all

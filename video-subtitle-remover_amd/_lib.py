@@ -242,6 +242,9 @@ SIGNATURES = {
     "vsr_key_apply_hold": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vsr_borrow_workspace_bytes": (_L, [_I, _I, _I]),
     "vsr_borrow_apply": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vsr_borrow_pan_workspace_bytes": (_L, [_I, _I, _I, _I, _I]),
+    "vsr_borrow_pan_search": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vsr_borrow_pan_apply": (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vsr_static_accum": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vsr_static_classify": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vsr_plan_consts": (_L, [_P, _P, _L]),

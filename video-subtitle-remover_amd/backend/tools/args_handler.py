@@ -68,6 +68,10 @@ def build_parser():
                              "shows the real picture at that pixel, take that frame's pixel instead of the fill, if the picture around the "
                              "inpainted pixels stood still between the two and the pixel lies within 24 levels of the fill (0 = off, at "
                              "most 8); sets VSR_BORROW")
+    parser.add_argument("--borrow-pan", type=int, default=None, metavar="P",
+                        help="with --borrow B: follow a camera that pans by whole pixels: per pair of frames a shift of up to P pixels "
+                             "per frame step, found on the picture around the inpainted pixels, is used where the picture did not stand "
+                             "still, and the other frame's pixel is read at the shifted place (0 = off, at most 8); sets VSR_BORROW_PAN")
     # not in the reference: every mode finds the static overlays of the clip itself and inpaints them on every frame (tools/logo_scan.py)
     parser.add_argument("--logo-scan", action="store_true",
                         help="every mode: one pass over the clip on the GPU first finds the rectangles that hold a static overlay (a "
@@ -133,6 +137,14 @@ def parse_args(argv=None):
                 raise ValueError("it borrows where --glyph-key T would show fill, and that is off: give both")
         except ValueError as e:
             parser.error(f"--borrow: {e}")
+    if args.borrow_pan is not None:
+        from .borrow import borrow_option, pan_option
+
+        try:
+            if pan_option(args.borrow_pan) and not borrow_option(args.borrow):
+                raise ValueError("it says how far --borrow B follows a pan, and that is off: give both")
+        except ValueError as e:
+            parser.error(f"--borrow-pan: {e}")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []
