@@ -847,6 +847,30 @@ int vsr_static_classify(const uint8_t* lo_dev, const uint8_t* hi_dev, const uint
                         float* grown_dev, uint8_t* moving_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Un-mixing translucent overlays (--logo-unblend, csrc/unmix_kernels.hip; the statement is tests/_unmix_statement.py, the design
+ * DESIGN.md 4.20): an overlay I = (1 - a) B + a L that --logo-scan found gives the picture back as B = (I - o) / g.  Integer, bit-exact;
+ * all pointers but `box` are device pointers, all work is issued on `stream`, nothing waits for the device.  backend/tools/unblend.py
+ * solves for the planes g and o on the host between the two.  Bad arguments (a null pointer, H or W <= 0, H * W * 3 >= 2^31, a stride
+ * smaller than the rows held, n outside 1..65535 (accum) or below 0 (apply), first not 0 or 1, a box that is empty or leaves the frame,
+ * rows that leave the frame, a misaligned plane) return VSR_ERR_ARG and launch nothing.
+ * ------------------------------------------------------------------------------------- */
+/* ONE launch over the n frames frames_dev + idx_dev[k] * frame_stride (uint8 [H][W][3], idx_dev: int32 frame numbers in a device array
+ * the caller owns), restricted to Gbox = [gy0, gy1) x [gx0, gx1): per byte of Gbox s1 = the sum and s2 = the sum of squares over the
+ * frames, uint32 [gy1 - gy0][gx1 - gx0][3] each.  first = 1 overwrites both planes; first = 0 continues them, so the pieces of a clip give
+ * what one call gives.  A call takes at most 65535 frames; the caller keeps the total of a continued sum at or below 65535, above
+ * which s2 could overflow (backend/tools/unblend.Moments refuses it).  A workgroup owns its bytes for all n frames: no atomics. */
+int vsr_unmix_accum(const uint8_t* frames_dev, int64_t frame_stride, const int32_t* idx_dev, int n, int H, int W, int gy0, int gy1, int gx0, int gx1,
+                    int first, uint32_t* s1_dev, uint32_t* s2_dev, void* stream);
+/* ONE launch, in place on frames_dev (n frames of uint8 [rows][W][3]: the rows [y0, y0 + rows) of the picture, they hold the fill) from
+ * src_dev (the same rows of the source, its own stride; src_dev == frames_dev with equal strides is allowed): box = host int32 [4]
+ * (ymin, ymax, xmin, xmax) of the area, g16_dev uint16 [ymax - ymin][xmax - xmin] the gain in Q8, o16_dev int16 [..][..][3] the offset in
+ * Q4.  Every pixel of the box inside the rows held with g >= 64 gets, per channel, num = 256 (16 I - o), den = 16 g,
+ * out = 0 if num < 0 else min(255, (num + den / 2) / den) of the source byte I; nothing else is written.  n = 0 or a box wholly outside
+ * the rows is success without a launch. */
+int vsr_unmix_apply(uint8_t* frames_dev, int64_t frame_stride, const uint8_t* src_dev, int64_t src_stride, const uint16_t* g16_dev,
+                    const int16_t* o16_dev, int n, int H, int W, int y0, int rows, const int32_t* box, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Plan introspection (host only, no GPU needed): the op list the engine runs for inpaint(L),
  * with symbolic buffers and the offset tables -- replayed on the CPU by tests/.
  * ------------------------------------------------------------------------------------- */

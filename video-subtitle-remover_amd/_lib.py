@@ -247,6 +247,8 @@ SIGNATURES = {
     "vsr_borrow_pan_apply": (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vsr_static_accum": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vsr_static_classify": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "vsr_unmix_accum": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "vsr_unmix_apply": (_I, [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vsr_plan_consts": (_L, [_P, _P, _L]),
     "vsr_plan_destroy": (None, [_P]),
     "vsr_plan_num_buffers": (_I, [_P]),

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ..config import config
-from ..tools import borrow, glyph_key, seam_feather
+from ..tools import borrow, glyph_key, seam_feather, unblend
 from ..tools.inpaint_tools import get_inpaint_area_by_mask, is_frame_number_in_ab_sections, threshold_mask
 from ..tools.video_io import ArrayWriter, device_bgr_to_planes, device_planes_to_bgr, open_video
 from ...engine import SttnEngine
@@ -105,7 +105,7 @@ class STTNInpaint:
         dev = self.engine.device
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(dev, non_blocking=True)
         dmask = torch.from_numpy(np.ascontiguousarray(mask[:, :, 0])).to(dev, non_blocking=True)
-        wanted = any(seam_feather.options()) or glyph_key.key_option()
+        wanted = any(seam_feather.options()) or glyph_key.key_option() or unblend.active()
         cmask = self.composite_mask(mask, thresholded=True) if wanted else None
         self.auto_chunk(frames, dmask, inpaint_area, cmask=cmask, mask_host=mask[:, :, 0])
         out = frames.cpu().numpy()
@@ -222,7 +222,8 @@ class STTNAutoInpaint:
         dmask = torch.from_numpy(np.ascontiguousarray(mask[y_lo:y_hi, :, 0])).to(engine.device) if inpaint_area else None
         mask_rows_host = mask[y_lo:y_hi, :, 0] if inpaint_area else None     # the engine reads the rows that hold the mask off this copy
         # --seam-feather, --regrain, --deflicker, --tone-match, --glyph-key: the composite mask of the FULL frame; a loop that hands the engine strip rows says which (STTNInpaint.auto_chunk)
-        cmask = self.sttn_inpaint.composite_mask(mask, thresholded=True) if ((feather or grain or flicker or tone or key) and inpaint_area) else None
+        # (--logo-unblend: plans in unblend's registry ask for it as well)
+        cmask = self.sttn_inpaint.composite_mask(mask, thresholded=True) if ((feather or grain or flicker or tone or key or unblend.active()) and inpaint_area) else None
         kept = {}
 
         def tick(original, frame):

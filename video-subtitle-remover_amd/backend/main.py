@@ -65,6 +65,9 @@ class SubtitleRemover:
         self.phase_seconds = {}
         self.resident_windows = None             # what a windowed run did (tools/resident_windows.WindowedClip.report); None: no such run
         self.static_areas = []                   # [(ymin, ymax, xmin, xmax)] that --logo-scan found (tools/logo_scan.py); run() fills it
+        self.unblend_plans = []                  # the areas --logo-unblend un-mixes (tools/unblend.Plan) and [(area, reason)] of those it
+        self.unblend_refusals = []               # leaves to inpainting; run() fills both
+        self._logo_scan = None                   # the scan with its sampled frames on the device, until the plans are made
 
     @property
     def video_writer(self):
@@ -297,12 +300,30 @@ class SubtitleRemover:
         (xmin, xmax, ymin, ymax) for the frames 1 .. frame_count; without such areas (the option off) the dictionary as it came"""
         if not self.static_areas:
             return sub_list
+        if self._logo_scan is not None:
+            # --logo-unblend: the plans, from the areas that meet no box of the text detector in any frame
+            self._make_unblend_plans({(ymin, ymax, xmin, xmax) for have in sub_list.values() for xmin, xmax, ymin, ymax in have})
         boxes = [(xmin, xmax, ymin, ymax) for ymin, ymax, xmin, xmax in self.static_areas]
         out = {}
         for no in range(1, self.frame_count + 1):
             have = list(sub_list.get(no, []))
             out[no] = have + [b for b in boxes if b not in have]
         return out
+
+    def _make_unblend_plans(self, text_boxes):
+        """--logo-unblend (tools/unblend.py): the plans of the areas the scan found, registered for the plugin calls of this run; an
+        area that meets one of `text_boxes` (ymin, ymax, xmin, xmax), or that cannot be un-mixed, is reported and inpainted as without
+        the option.  The scan's sampled frames leave the device here."""
+        from .tools import unblend
+
+        scan, self._logo_scan = self._logo_scan, None
+        self.unblend_plans, self.unblend_refusals = self._timed("logo unblend plans", unblend.make_plans, scan, self.static_areas,
+                                                                sorted(text_boxes))
+        unblend.register(self.unblend_plans)
+        for plan in self.unblend_plans:
+            self.append_output(f"logo unblend: area {plan.box} is un-mixed (gain {plan.level}/256)")
+        for area, reason in self.unblend_refusals:
+            self.append_output(f"logo unblend: area {area} stays inpainted ({reason})")
 
     @staticmethod
     def _clip_kw(clip):
@@ -606,20 +627,45 @@ class SubtitleRemover:
         from .tools import logo_scan
 
         scan = logo_scan.refuse_ranks(self._distributed())   # --logo-scan: a bad value or several ranks, likewise
+        from .tools import unblend
+
+        unmix = unblend.refuse()                             # --logo-unblend: a bad value, or on without --logo-scan, likewise
+        try:
+            self._run(scan, unmix, start_time)
+        finally:
+            if unmix:
+                unblend.clear()
+                self._logo_scan = None
+
+    def _run(self, scan, unmix, start_time):
+        """run() behind its refusals"""
+        from .tools import logo_scan
+
         if self._video_writer is None and self.is_path:
             self._y4m_like()                                             # a sink that cannot be made fails before any work is done
         mode = config.inpaintMode.value
         if scan:
             # one pass over the clip before the sink is made: a scan that must fail (a picture, a clip of fewer than 16 frames) leaves no file
-            self.static_areas = self._timed("logo scan", logo_scan.find_areas, self.video_path, device=self._device_index(),
-                                            report=self.append_output)
+            if unmix:
+                # (--logo-unblend: the sampled frames stay on the device until the plans are made)
+                self._logo_scan = self._timed("logo scan", logo_scan.run_scan, self.video_path, device=self._device_index(),
+                                              report=self.append_output, keep=True)
+                self.static_areas = self._logo_scan.found
+                if not self.static_areas:
+                    self._logo_scan = None                               # nothing to un-mix: the frames leave the device now
+            else:
+                self.static_areas = self._timed("logo scan", logo_scan.find_areas, self.video_path, device=self._device_index(),
+                                                report=self.append_output)
             self.append_output(f"logo scan: {len(self.static_areas)} static area{'s' if len(self.static_areas) != 1 else ''} "
                                f"(ymin, ymax, xmin, xmax): {self.static_areas}")
             if mode == InpaintMode.STTN_AUTO:
                 # the areas join the boxes of -c; without -c they are the mask, in place of the whole frame
                 if len(self.sub_areas) == 0 and len(self.static_areas) == 0:
                     raise Exception(f"No static overlay found in {self.video_path} and no subtitle area given (-c)")
+                boxed = list(self.sub_areas)
                 self.sub_areas.extend(a for a in self.static_areas if a not in self.sub_areas)
+                if unmix:
+                    self._make_unblend_plans(boxed)                      # an area that meets a box of -c stays inpainted
         if len(self.sub_areas) == 0:
             self.sub_areas.append((0, self.frame_height, 0, self.frame_width))
         if self.is_picture:
@@ -663,7 +709,7 @@ FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDE
             ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str),
             ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str), ("borrow", "VSR_BORROW", str),
             ("borrow_pan", "VSR_BORROW_PAN", str),
-            ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"))
+            ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"), ("logo_unblend", "VSR_LOGO_UNBLEND", lambda _: "1"))
 
 
 def main(argv=None):

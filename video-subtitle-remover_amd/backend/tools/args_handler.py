@@ -79,6 +79,13 @@ def build_parser():
                              "and inpaints them on every frame; sttn-auto: they join the -c boxes and, without -c, replace the "
                              "whole-frame default; the other modes: -c keeps restricting the text detector only; finds nothing in a "
                              "static shot and no overlay larger than a third of the frame; needs 16 frames; one process; sets VSR_LOGO_SCAN=1")
+    # not in the reference: a translucent overlay found by --logo-scan is un-mixed, not inpainted (tools/unblend.py)
+    parser.add_argument("--logo-unblend", action="store_true",
+                        help="with --logo-scan: an overlay that is translucent, I = (1 - a) B + a L, gives the real picture back by a "
+                             "division instead of an inpainted one: per pixel of a found area the gain 1 - a and the offset a L are "
+                             "estimated from the frames the scan sampled, and every frame's area gets (I - a L) / (1 - a) of its "
+                             "source; the fill stays under the opaque part, and an area whose overlay is opaque, too faint, in a "
+                             "still shot or crossed by a text box is inpainted as before; sets VSR_LOGO_UNBLEND=1")
     return parser
 
 
@@ -145,6 +152,8 @@ def parse_args(argv=None):
                 raise ValueError("it says how far --borrow B follows a pan, and that is off: give both")
         except ValueError as e:
             parser.error(f"--borrow-pan: {e}")
+    if args.logo_unblend and not args.logo_scan:
+        parser.error("--logo-unblend: it un-mixes the areas --logo-scan finds, and that is off: give both")
     args.inpaint_mode = InpaintMode[args.inpaint_mode.replace("-", "_").upper()]
     if args.subtitle_area_coords is None:
         args.subtitle_area_coords = []

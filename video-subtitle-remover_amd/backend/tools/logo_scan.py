@@ -22,6 +22,9 @@ frame (a letterbox, the set of a studio: not told apart from the picture).
 Off (the default): nothing here is called but scan_option, no launch, no byte written that was not before.  The option is read here
 and nowhere else (scan_option: --logo-scan sets VSR_LOGO_SCAN=1).  Several ranks are refused (refuse_ranks) before any work, as
 --regrain refuses them.
+
+--logo-unblend (tools/unblend.py) estimates its planes from the same sampled frames: run_scan(keep=True) returns the Scan with
+them still on the device (Scan.pieces), find_areas is run_scan without keeping.
 """
 import ctypes as C
 import os
@@ -104,13 +107,16 @@ class Scan:
     """the per-pixel state of one scan on one device.  feed() takes sampled frames in any pieces -- the planes are integers, min, max
     and a count, so the pieces give what one call gives -- and areas() ends the scan."""
 
-    def __init__(self, H, W, device=0):
+    def __init__(self, H, W, device=0, keep=False):
+        """keep: the frames fed stay referenced in `pieces` [(frames, idx)] until the scan is dropped (--logo-unblend estimates its planes
+        from them, tools/unblend.py): a resident clip as it is, an uploaded batch as uploaded"""
         import torch
 
         if not torch.cuda.is_available():
             raise RuntimeError("the logo scan runs on the MI355X path only: no HIP device available")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.H, self.W, self.fed = int(H), int(W), 0
+        self.keep, self.pieces = bool(keep), []
         self.lo = torch.empty((H, W), dtype=torch.uint8, device=self.device)
         self.hi = torch.empty((H, W), dtype=torch.uint8, device=self.device)
         self.edges = torch.empty((H, W), dtype=torch.int16, device=self.device)      # (uint16 to the kernels)
@@ -135,6 +141,8 @@ class Scan:
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             check(lib.vsr_static_accum(_p(frames), stride, _p(idx_dev), len(idx), self.H, self.W, GE, 0 if self.fed else 1,
                                        _p(self.lo), _p(self.hi), _p(self.edges), stream))
+        if self.keep:
+            self.pieces.append((frames, idx))
         self.fed += len(idx)
         stats["frames"] += len(idx)
         stats["accum_launches"] += 1
@@ -191,7 +199,13 @@ class Scan:
 
 
 def find_areas(video, device=0, clip=None, report=None):
-    """the static overlays of a video -> [(ymin, ymax, xmin, xmax)], sorted by (ymin, xmin).  `video`: a path or frame source accepted
+    """the static overlays of a video -> [(ymin, ymax, xmin, xmax)], sorted by (ymin, xmin): run_scan(...).found"""
+    return run_scan(video, device=device, clip=clip, report=report).found
+
+
+def run_scan(video, device=0, clip=None, report=None, keep=False):
+    """-> the Scan of a video, its areas [(ymin, ymax, xmin, xmax)], sorted by (ymin, xmin), in `found`; keep: its sampled frames stay on
+    the device with it (Scan.pieces: at most 120 frames).  `video`: a path or frame source accepted
     by video_io.open_video; clip: the same video resident in HBM (tools/resident.ResidentClip) -- the kernel then reads the sampled
     frames where they are, in one launch.  Without one (host frames, or a windowed clip, which holds no frame yet) the video is read
     once more and its sampled frames are uploaded in batches.  report(text), if given, is told of components dropped over MAX_AREAS."""
@@ -202,7 +216,7 @@ def find_areas(video, device=0, clip=None, report=None):
     if clip is not None and not getattr(clip, "windowed", False):
         N, H, W, _ = clip.frames.shape
         idx = sample_indices(N)
-        scan = Scan(H, W, clip.frames.device)
+        scan = Scan(H, W, clip.frames.device, keep=keep)
         scan.feed(clip.frames, idx)
     else:
         reader = open_video(video)
@@ -210,7 +224,7 @@ def find_areas(video, device=0, clip=None, report=None):
             info = reader.info()
             wanted = set(sample_indices(info["len"]))
             H, W = info["H_ori"], info["W_ori"]
-            scan = Scan(H, W, device)
+            scan = Scan(H, W, device, keep=keep)
             batch, no = [], 0
 
             def flush():
@@ -238,4 +252,5 @@ def find_areas(video, device=0, clip=None, report=None):
     if scan.dropped and report is not None:
         report(f"logo scan: {scan.dropped} more static component{'s' if scan.dropped != 1 else ''} found than the {MAX_AREAS} kept "
                "(the largest); box the others with -c")
-    return areas
+    scan.found = areas
+    return scan

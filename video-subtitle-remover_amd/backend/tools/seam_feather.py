@@ -43,6 +43,12 @@ deflicker -> regrain -> borrow -> glyph-key -> feather.  A borrowed pixel is rea
 regrain the model's fill run before it and do not touch it; the key then judges the frames as the borrow left them.  It needs T > 0 and
 the plugin's sample rows (the ring of --regrain gates it); B is read through borrow.borrow_option(), and refuse_ranks_all() makes its
 refusals too.  B = 0: the calls above and nothing else.
+
+--logo-unblend (tools/unblend.py) is the seventh pass and the last: body -> tone-match -> deflicker -> regrain -> borrow ->
+glyph-key -> feather -> unblend.  Inside the areas of --logo-scan whose translucent overlay it can un-mix it writes the un-mixed source
+over whatever stands there; that is real picture, so no cosmetic pass may touch it.  It reads no option here: the plans of the run are
+in unblend's registry (SubtitleRemover.run() sets it), and with plans registered a call clones its source even when every other option
+is off.  No plans (the option off): the calls above and nothing else.
 """
 import collections
 import ctypes as C
@@ -53,6 +59,7 @@ import numpy as np
 
 from . import borrow as borrow_pass
 from . import deflicker, glyph_key, regrain, tone_match
+from . import unblend as unblend_pass
 
 MAX_FEATHER = 64
 ENV = "VSR_SEAM_FEATHER"
@@ -163,7 +170,7 @@ def composite(frames, src, d, feather):
     return frames
 
 
-def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0, tone=0, key=0, borrow=0):
+def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=None, flicker=0, tone=0, key=0, borrow=0, unmix=None):
     """body(frames) inpaints the device tensor `frames` in place (today's call); with F > 0 and a non-empty composite mask the frames
     come back as the definition's.  cmask: the FULL-frame composite mask (host uint8) or a callable that makes it; rows = (y_lo, y_hi):
     `frames` holds these rows of the frame only (sttn-auto's strip rows) -- d is computed on the full frame and sliced, so a mask that
@@ -177,12 +184,15 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
     key = T of --glyph-key (tools/glyph_key.py): with T > 0 the source is kept, against the same clone, wherever the fill as the other
     three passes left it only repeats it; the composite follows.
     borrow = B of --borrow (tools/borrow.py): with B > 0, T > 0 and more than one frame, a pixel the key would show fill at takes the
-    source pixel of a frame of the call within B frames that shows the real picture there, in front of the key."""
+    source pixel of a frame of the call within B frames that shows the real picture there, in front of the key.
+    unmix = the plans of --logo-unblend (tools/unblend.py), None: the run's (unblend.active()): with plans, every area of theirs gets
+    its un-mixed source from the same clone behind the composite."""
+    unmix = unblend_pass.active() if unmix is None else unmix
     if frames.shape[0] < 2:
         flicker = 0                          # one frame has no neighbour
     if frames.shape[0] < 2 or not key:
         borrow = 0
-    if not (feather or grain or flicker or tone or key) or frames.shape[0] == 0:
+    if not (feather or grain or flicker or tone or key or unmix) or frames.shape[0] == 0:
         return body(frames)
     cm = cmask() if callable(cmask) else cmask
     if not cm.any():
@@ -212,14 +222,18 @@ def device_call(frames, cmask, body, feather, rows=None, grain=0, sample_rows=No
         glyph_key.apply(frames, src, keyed, key, y0=0 if rows is None else rows[0])
     if feather:
         composite(frames, src, d, feather)
+    if unmix:
+        unblend_pass.apply(frames, src, unmix, y0=0 if rows is None else rows[0], H=cm.shape[0])
     return frames if out is None else out
 
 
-def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lookahead=None):
+def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lookahead=None, unmix=None):
     """The __call__ of a plugin under the option: body(input_frames, input_mask[, context=][, lookahead=]) is the plugin's call as it
     has always been (a list of HxWx3 arrays -> fresh arrays; a uint8 [n,H,W,3] device tensor -> inpainted in place and returned).
     plugin.composite_mask(input_mask) names the pixels it blends under; device: where the list form uploads to.  Context frames
-    of either kind (in front of the batch, behind it) are handed through and take no part in the composite."""
+    of either kind (in front of the batch, behind it) are handed through and take no part in the composite.  unmix: the plans of
+    --logo-unblend, None: the run's."""
+    u = unblend_pass.active() if unmix is None else unmix
     kw = {} if context is None else {"context": context}
     if lookahead is not None:
         kw["lookahead"] = lookahead
@@ -228,21 +242,21 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
     b = borrow_pass.borrow_option() if t else 0
     if len(input_frames) < 2:
         r = b = 0                            # one frame has no neighbour
-    if not (f or g or r or s or t):
+    if not (f or g or r or s or t or u):
         return body(input_frames, input_mask, **kw)
     import torch
 
     sample_rows = plugin.sample_rows(input_mask) if (g or r or s or b) else None
     if isinstance(input_frames, torch.Tensor):
         return device_call(input_frames, lambda: plugin.composite_mask(input_mask), lambda d: body(d, input_mask, **kw), f,
-                           grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t, borrow=b)
+                           grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t, borrow=b, unmix=u)
     if len(input_frames) == 0:
         return body(input_frames, input_mask, **kw)
     cm = plugin.composite_mask(input_mask)
     if not cm.any():
         return body(input_frames, input_mask, **kw)
     if not getattr(plugin, "accepts_device_frames", False):
-        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the six passes
+        # a body that works on host arrays (opencv through cv2): its fill and the source go up for the seven passes
         fill = body(input_frames, input_mask, **kw)
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(fill))).to(device)
         src = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
@@ -258,11 +272,13 @@ def plugin_call(plugin, body, input_frames, input_mask, device, context=None, lo
             glyph_key.apply(frames, src, glyph_key.mask(cm, frames.device), t)
         if f:
             composite(frames, src, alpha(cm, f, frames.device), f)
+        if u:
+            unblend_pass.apply(frames, src, u, H=cm.shape[0])
     else:
         frames = torch.from_numpy(np.ascontiguousarray(np.stack(input_frames))).to(device)
         kw = {name: torch.from_numpy(np.ascontiguousarray(np.stack(c))).to(device)
               for name, c in (("context", context), ("lookahead", lookahead)) if c is not None and len(c)}
         device_call(frames, cm, lambda d: body(d, input_mask, **kw), f, grain=g, sample_rows=sample_rows, flicker=r, tone=s, key=t,
-                    borrow=b)
+                    borrow=b, unmix=u)
     out = frames.cpu().numpy()
     return [out[i] for i in range(out.shape[0])]
