@@ -917,6 +917,7 @@ typedef struct VsrSoftmaxInfo {
     float scale;
 } VsrSoftmaxInfo;
 
+/* the plan of the handle's arithmetic (vsr_sttn_set_precision; exact fp32 unless set) and lanes */
 int vsr_plan_create(const vsr_sttn_t* h, int L, vsr_plan_t** out);
 int vsr_plan_create_rows(const vsr_sttn_t* h, int L, int row_lo, int row_hi, vsr_plan_t** out);   /* the decoder on model rows [row_lo, row_hi) only */
 int vsr_plan_create_box(const vsr_sttn_t* h, int L, int row_lo, int row_hi, int col_lo, int col_hi, vsr_plan_t** out);   /* ... and columns */

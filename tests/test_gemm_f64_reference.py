@@ -103,6 +103,42 @@ def test_split_format_round_trip():
     assert np.array_equal(np.sort(np.concatenate([hi_i, lo_i])), np.sort(np.concatenate([2 * cells, 2 * cells + 1])))
 
 
+@pytest.mark.parametrize("bm,bn,bmode", [(128, 128, 1), (128, 64, 1), (256, 32, 0), (256, 64, 0), (128, 128, 0)],
+                         ids=["128x128-KN", "128x64-KN", "256x32-NK", "256x64-NK", "128x128-NK"])
+def test_make_case_on_every_tile_and_layout_the_gpu_tests_use(bm, bn, bmode):
+    """make_case / physical / reference64 at the epilogue matrix's shape (M = 2 bm + 44, N = 2 bn + 8, K = 96) on the tiles and
+    layouts tests/test_gpu_gemm_family.py launches: the written cells are the descriptor's, the float64 reference agrees with the
+    fp32 replay inside the derived bound, every table entry -- the padded rows a tile reads but never stores included -- addresses
+    32 floats inside its buffer, and the split-format image holds hi / lo halves in exactly the chunks the tables address (KN: the K
+    rows of B times the n chunks)."""
+    rng = np.random.default_rng(bm + bn + bmode)
+    M, N, K = 2 * bm + 44, 2 * bn + 8, 96
+    c = g64.make_case(rng, M, N, K, bm, bn, bmode, bias=True, act=1, residual=True)
+    assert (c.tilesM, c.tilesN) == (3, 3) and len(c.rowA) == len(c.rowC) == len(c.rowR) == 3 * bm and len(c.colC) == 3 * bn // 32
+    assert len(c.rowB) == (K if bmode else 3 * bn) and len(c.colB) == (3 * bn // 32 if bmode else K // 32)
+    for rows, cols, buf in ((c.rowA, c.colA, c.Abuf), (c.rowB, c.colB, c.Bbuf), (c.rowC, c.colC, c.Cbuf), (c.rowR, c.colC, c.Rbuf)):
+        assert rows.min() >= 0 and cols.min() >= 0 and rows.max() + cols.max() + 32 <= buf.size
+        assert np.all(rows % 4 == 0) and np.all(cols % 32 == 0)
+    r = g64.reference64(c, g64.operand_model(3))
+    assert np.array_equal(np.sort(r.cells.reshape(-1)), np.flatnonzero(_written_mask(c)))
+    replay = _reference(c)
+    err = np.abs(replay[r.cells].astype(np.float64) - r.ref)
+    assert np.all(err <= g64.bound(r)) and err.max() > 0
+    p = g64.physical(c, g64.operand_model(5))
+    for buf, orig, rows, cols in ((p.A, c.Abuf, c.rowA, c.colA), (p.B, c.Bbuf, c.rowB, c.colB), (p.R, c.Rbuf, c.rowR[:M], c.colC)):
+        starts = np.unique(g64.chunk_starts(rows, cols))
+        cells = (starts[:, None] + np.arange(32)[None, :]).reshape(-1)
+        hi, lo = g64.split_halves(orig[cells])
+        h16 = buf.view(np.uint16)[(2 * starts[:, None] + np.arange(64)[None, :])]         # a chunk: 32 hi halves, then 32 lo halves
+        assert np.array_equal(h16[:, :32].reshape(-1), hi.view(np.uint16)) and np.array_equal(h16[:, 32:].reshape(-1), lo.view(np.uint16))
+        other = np.setdiff1d(np.arange(orig.size), cells)
+        assert np.array_equal(buf[other].view(np.uint32), orig[other].view(np.uint32))
+    poisoned = g64.make_case(np.random.default_rng(bm + bn + bmode), M, N, K, bm, bn, bmode, bias=True, act=1, residual=True, poison=True)
+    assert np.all(poisoned.Abuf[poisoned.rowA[M:, None] + poisoned.colA[None, :]] == 1e6) and np.array_equal(poisoned.rowA[:M], c.rowA[:M])
+    assert poisoned.rowA.max() + poisoned.colA.max() + 32 <= poisoned.Abuf.size
+    assert np.array_equal(g64.reference64(poisoned, g64.operand_model(3)).ref, r.ref)
+
+
 def test_physical_buffers_and_footprint_helpers():
     """physical() writes split format exactly where a split-format variant reads it; untouched() sees one stray uint16"""
     rng = np.random.default_rng(12)

@@ -118,7 +118,13 @@ def _check_all(L, outs, what, key=None):
 
 # ---- D1: tile hand-over -------------------------------------------------------------------------------------------------------------
 HANDOVER = [(3, "128x64", 0), (4, "128x64", 0), (7, "128x64", 0), (5, "128x64", 0), (6, "128x64", 0), (3, "128x64", 1), (5, "128x64", 1),
-            (3, "128x128", 0), (3, "256x64", 0), (3, "256x32", 0), (6, "256x128", 0), (5, "256x256", 0), (6, "256x256", 0)]
+            (3, "128x128", 0), (3, "256x64", 0), (3, "256x32", 0), (6, "256x128", 0), (5, "256x256", 0), (6, "256x256", 0),
+            # what the engines launch besides (tests/test_gemm_launch_census.py holds this list to their plans): the generator's fp16 mode on
+            # 128x128, LaMa's Fourier stages (KN 128x128), the narrow and first / last convs (256x64, 256x32), P.V in every arithmetic
+            (4, "128x128", 0), (4, "256x64", 0), (4, "256x32", 0), (4, "128x64", 1), (4, "128x128", 1),
+            (7, "128x128", 0), (7, "256x64", 0), (7, "256x32", 0), (7, "128x64", 1), (7, "128x128", 1),
+            (5, "256x64", 0), (5, "256x32", 0), (6, "256x64", 0), (6, "256x32", 0), (6, "128x128", 0), (6, "128x64", 1),
+            (3, "128x128", 1)]
 # K (chunks 1, 2, 3, 5 and 3 cut 2 + 1), bias, act, residual, alpha, splitK, chunksPerSplit
 EPILOGUES = [(32, False, 0, False, 1.0, 1, None), (64, True, 1, True, 1.0, 1, None), (96, True, 2, False, 0.5, 1, None),
              (160, False, POST_RELU, True, 1.0, 1, None), (96, False, 0, False, 1.0, 2, 2)]
@@ -181,7 +187,15 @@ def test_tile_handover(built_lib, gpu_device, variant, tile, bmode, wide):
 EPI_KERNELS = [(1, "128x64", 0, 0), (1, "128x64", 1, 0), (3, "128x64", 0, 0), (3, "128x64", 1, 0), (4, "128x64", 0, 0), (7, "128x64", 0, 0),
                (7, "128x64", 1, 0), (5, "128x64", 0, 0), (5, "128x64", 0, 1), (6, "128x64", 0, 0), (6, "128x64", 0, 1),
                (6, "256x128", 0, 0), (6, "256x128", 0, 1), (5, "256x256", 0, 0), (5, "256x256", 0, 1), (6, "256x256", 0, 0),
-               (6, "256x256", 0, 1)]
+               (6, "256x256", 0, 1),
+               # (see HANDOVER)
+               (4, "128x128", 0, 0), (4, "256x64", 0, 0), (4, "256x32", 0, 0), (4, "128x64", 1, 0), (4, "128x128", 1, 0),
+               (7, "128x128", 0, 0), (7, "256x64", 0, 0), (7, "256x32", 0, 0), (7, "128x128", 1, 0),
+               (5, "256x64", 0, 0), (5, "256x64", 0, 1), (5, "256x32", 0, 0), (5, "256x32", 0, 1), (5, "128x64", 1, 0), (5, "128x64", 1, 1),
+               (6, "256x64", 0, 0), (6, "256x64", 0, 1), (6, "256x32", 0, 0), (6, "256x32", 0, 1), (6, "128x128", 0, 0),
+               (6, "128x128", 0, 1), (6, "128x64", 1, 0), (6, "128x64", 1, 1),
+               (1, "128x128", 0, 0), (1, "256x64", 0, 0), (1, "256x32", 0, 0), (1, "128x128", 1, 0),
+               (3, "128x128", 0, 0), (3, "256x64", 0, 0), (3, "256x32", 0, 0), (3, "128x128", 1, 0)]
 
 
 def _epilogue_cases(bm, bn, bmode, split_tensors, out_split):
@@ -244,56 +258,61 @@ def test_variant7_is_served_where_its_kernels_exist(built_lib, gpu_device):
 
 
 # ---- D3: range guard ----------------------------------------------------------------------------------------------------------------
-GUARDED = [(4, "128x64"), (7, "128x64"), (5, "128x64"), (6, "128x64"), (6, "256x128"), (5, "256x256"), (6, "256x256")]
+GUARDED = [(4, "128x64", 0), (7, "128x64", 0), (5, "128x64", 0), (6, "128x64", 0), (6, "256x128", 0), (5, "256x256", 0), (6, "256x256", 0),
+           # (see HANDOVER)
+           (4, "128x128", 0), (4, "256x64", 0), (4, "256x32", 0), (7, "128x128", 0), (7, "256x64", 0), (7, "256x32", 0),
+           (5, "256x64", 0), (5, "256x32", 0), (6, "256x64", 0), (6, "256x32", 0), (6, "128x128", 0),
+           (4, "128x64", 1), (4, "128x128", 1), (7, "128x64", 1), (7, "128x128", 1), (5, "128x64", 1), (6, "128x64", 1)]
 
 
-def _guard_case(bm, bn, seed, **kw):
-    return g64.make_case(np.random.default_rng(seed), 2 * bm + 44, 2 * bn + 8, 96, bm, bn, 0, bias=True, act=kw.pop("act", 1), residual=True, **kw)
+def _guard_case(bm, bn, bmode, seed, **kw):
+    return g64.make_case(np.random.default_rng(seed), 2 * bm + 44, 2 * bn + 8, 96, bm, bn, bmode, bias=True, act=kw.pop("act", 1), residual=True, **kw)
 
 
 def _poke_A(c, m, k, value):
     c.Abuf[c.rowA[m] + c.colA[k // 32] + k % 32] = value
 
 
-@pytest.mark.parametrize("variant,tile", GUARDED, ids=[f"v{v}-{t}" for v, t in GUARDED])
-def test_range_guard(built_lib, gpu_device, variant, tile):
+@pytest.mark.parametrize("variant,tile,bmode", GUARDED, ids=[f"v{v}-{t}{'-KN' if m else ''}" for v, t, m in GUARDED])
+def test_range_guard(built_lib, gpu_device, variant, tile, bmode):
     """The range flag of the reduced-precision kernels, through vsr_run_gather_gemm_flagged: (i) benign operands leave it 0 and the
     flagged launch writes the unflagged launch's bytes; (ii) one operand of 1e6 (hi half inf) in a stored row raises it, in an
     interior and in a border tile; (iii) a finite result beyond 65504 raises it in split format only; (iv) 1e6 in the padding
-    rows of A and B -- table rows m >= M, n >= N, which the tiles read but never store -- leaves it 0 and every output byte alone."""
+    rows of A and B -- table rows m >= M, n >= N (KN: of A alone, B has no row per n), which the tiles read but never store -- leaves
+    it 0 and every output byte alone."""
     cfg, bm, bn = TILES[tile]
     seed = 300 + variant + bn
     has_split = g64.operand_model(variant).split_tensors
-    what = f"guard v{variant} {tile}"
+    what = f"guard v{variant} {tile}{' KN' if bmode else ''}"
     # (i)
-    benign = _guard_case(bm, bn, seed)
+    benign = _guard_case(bm, bn, bmode, seed)
     L = _Launch(built_lib, gpu_device, [benign], variant)
-    plain = L.run(cfg, 0)[0]
+    plain = L.run(cfg, bmode)[0]
     L.reset()
-    outs, flag = L.run_flagged(cfg, 0)
+    outs, flag = L.run_flagged(cfg, bmode)
     assert flag == 0, f"{what} (i): benign operands raised the flag ({flag})"
     assert _same_bytes(outs[0], plain)
     _check(benign, variant, outs[0], L.before[0], f"{what} (i)")
     # (ii)
     for where, m in (("interior", 5), ("border", benign.M - 1)):
-        c = _guard_case(bm, bn, seed)
+        c = _guard_case(bm, bn, bmode, seed)
         _poke_A(c, m, 40, 1e6)
-        _, flag = _Launch(built_lib, gpu_device, [c], variant).run_flagged(cfg, 0)
+        _, flag = _Launch(built_lib, gpu_device, [c], variant).run_flagged(cfg, bmode)
         assert flag & 1, f"{what} (ii): 1e6 in row {m} ({where} tile) left the flag at {flag}"
     # (iii)
     for osp in ((0, OUT_SPLIT) if has_split else (0,)):
-        c = _guard_case(bm, bn, seed, act=1 | osp)
+        c = _guard_case(bm, bn, bmode, seed, act=1 | osp)
         c.biasv[:] = 1e5
         L3 = _Launch(built_lib, gpu_device, [c], variant)
-        outs, flag = L3.run_flagged(cfg, 0)
+        outs, flag = L3.run_flagged(cfg, bmode)
         assert flag == (1 if osp else 0), f"{what} (iii): results of 1e5 with out_split={bool(osp)} gave flag {flag}"
         if not osp:
             _check(c, variant, outs[0], L3.before[0], f"{what} (iii)")
     # (iv)
-    c = _guard_case(bm, bn, seed, poison=True)
+    c = _guard_case(bm, bn, bmode, seed, poison=True)
     assert np.array_equal(c.Cbuf, benign.Cbuf) and np.array_equal(c.rowC, benign.rowC)
     L4 = _Launch(built_lib, gpu_device, [c], variant)
-    outs, flag = L4.run_flagged(cfg, 0)
+    outs, flag = L4.run_flagged(cfg, bmode)
     assert _same_bytes(outs[0], plain), f"{what} (iv): operands behind the padding rows changed stored bytes"
     _check(c, variant, outs[0], L4.before[0], f"{what} (iv)")
     assert flag == 0, f"{what} (iv): 1e6 where nothing is stored raised the flag ({flag})"

@@ -1468,13 +1468,14 @@ int vsr_cv2_linear_tables(int ssize, int dsize, int clamp_x, int32_t* ofs, int16
 }
 
 // ---- plan introspection (host only) ------------------------------------------------------
+// the plan of the handle's arithmetic (vsr_sttn_set_precision; 0 unless set): modes 1 .. 3 have no fused softmax, so their P.V is a plain KN GEMM
 int vsr_plan_create(const vsr_sttn_t* h, int L, vsr_plan_t** out)
 {
     if (!h || !out || L <= 0) return fail(VSR_ERR_ARG, "bad argument");
     if (!h->model.packed_ready()) return fail(VSR_ERR_STATE, "model not finalized");
     try {
         std::unique_ptr<vsr_plan> p(new vsr_plan);
-        p->plan.reset(new Plan(h->model, L, 0, h->lanes));
+        p->plan.reset(new Plan(h->model, L, h->precision, h->lanes));
         *out = p.release();
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());
@@ -1487,7 +1488,7 @@ int vsr_plan_create_rows(const vsr_sttn_t* h, int L, int row_lo, int row_hi, vsr
     if (!h->model.packed_ready()) return fail(VSR_ERR_STATE, "model not finalized");
     try {
         std::unique_ptr<vsr_plan> p(new vsr_plan);
-        p->plan.reset(new Plan(h->model, L, 0, h->lanes, row_lo, row_hi));
+        p->plan.reset(new Plan(h->model, L, h->precision, h->lanes, row_lo, row_hi));
         *out = p.release();
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());
@@ -1500,7 +1501,7 @@ int vsr_plan_create_box(const vsr_sttn_t* h, int L, int row_lo, int row_hi, int 
     if (!h->model.packed_ready()) return fail(VSR_ERR_STATE, "model not finalized");
     try {
         std::unique_ptr<vsr_plan> p(new vsr_plan);
-        p->plan.reset(new Plan(h->model, L, 0, h->lanes, row_lo, row_hi, col_lo, col_hi));
+        p->plan.reset(new Plan(h->model, L, h->precision, h->lanes, row_lo, row_hi, col_lo, col_hi));
         *out = p.release();
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());
@@ -1517,7 +1518,7 @@ int vsr_plan_create_ctx2(const vsr_sttn_t* h, int L, int n_ctx, int n_after, int
     if (!h->model.packed_ready()) return fail(VSR_ERR_STATE, "model not finalized");
     try {
         std::unique_ptr<vsr_plan> p(new vsr_plan);
-        p->plan.reset(new Plan(h->model, L, 0, h->lanes, row_lo, row_hi, col_lo, col_hi, n_ctx, n_after));
+        p->plan.reset(new Plan(h->model, L, h->precision, h->lanes, row_lo, row_hi, col_lo, col_hi, n_ctx, n_after));
         *out = p.release();
     } catch (const std::exception& e) {
         return fail(VSR_ERR_ARG, std::string("plan: ") + e.what());
