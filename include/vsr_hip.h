@@ -538,6 +538,47 @@ int vsr_telea_plan_weights(const vsr_telea_t* h, float* w, uint8_t* flags);   /*
 int vsr_telea_inpaint(vsr_telea_t* h, uint8_t* frames_dev, int64_t frame_stride, int n, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * --opencv-fill exemplar: a PatchMatch exemplar fill, coarse to fine, for --inpaint-mode opencv (the statement is
+ * tests/_exemplar_statement.py, the design DESIGN.md 4.21).  One handle holds one mask's plan: pyramid sizes, valid sources,
+ * targets, tiles and the coarsest level's interpolation offsets depend on the mask alone and are built on the host by set_mask;
+ * inpaint runs the kernels over all n frames of a call together, on the caller's stream.
+ * ------------------------------------------------------------------------------------- */
+typedef struct vsr_exemplar vsr_exemplar_t;
+int vsr_exemplar_create(vsr_exemplar_t** out, int device);         /* device < 0: host-side plan only (plan tests) */
+void vsr_exemplar_destroy(vsr_exemplar_t* h);
+/* mask: HOST uint8 [H][W], non-zero = fill.  Builds the plan and, with a device, uploads it (synchronous).  A set mask that leaves
+ * no valid source at level 0 (a whole-frame mask, a frame smaller than 7x7) is refused: VSR_ERR_ARG.  An empty mask has 0 levels. */
+int vsr_exemplar_set_mask(vsr_exemplar_t* h, const uint8_t* mask_host, int H, int W);
+int vsr_exemplar_plan_levels(const vsr_exemplar_t* h);             /* pyramid levels (0 for an empty mask), -1 without a mask */
+/* read-back hooks of the tests.  level_info: int64 [VSR_EX_INFO_LEN] = H, W, sources, targets, tiles, hole pixels, and the box of
+ * the targets y0, x0, h, w (the match fields cover it). */
+enum { VSR_EX_INFO_LEN = 10 };
+int vsr_exemplar_plan_level_info(const vsr_exemplar_t* h, int level, int64_t* out);
+/* any pointer may be null: src int16 [sources][2] and tgt int16 [targets][2] (y, x; raster order), tiles int32 [tiles][2] (ty, tx of
+ * the 16 x 16 cells that hold a target), cls uint8 [H][W] (1 = hole, 2 = valid source, 4 = target) */
+int vsr_exemplar_plan_read(const vsr_exemplar_t* h, int level, int16_t* src, int16_t* tgt, int32_t* tiles, uint8_t* cls);
+/* the coarsest level's table, int32 [its hole pixels][6]: y, x, distance to the known pixel left, right, above, below (0: none) */
+int vsr_exemplar_plan_init(const vsr_exemplar_t* h, int32_t* table);
+int64_t vsr_exemplar_workspace_bytes(const vsr_exemplar_t* h, int n);   /* for a call of n frames; -1 without a mask */
+/* where a level lives in the workspace of a call of n frames, int64 [5]: byte offset of its images (-1: level 0, the frames
+ * themselves), bytes per image, byte offsets of match fields A and B, bytes per frame of a field.  A field is uint32 [n][h][w] over
+ * the targets' box: y in the low half, x in the high half (an int16 pair), 0xFFFFFFFF where there is no target. */
+int vsr_exemplar_layout(const vsr_exemplar_t* h, int n, int level, int64_t* out);
+/* one launch.  DOWN: level (>= 1) from level - 1.  INIT: the coarsest level's hole content.  UP: the level's initial field into A and
+ * B, from level + 1's A (the coarsest: from the hash).  SEARCH: one pass, reads B if from_b else A, writes the other.  VOTE: the
+ * hole pixels from B if from_b else A. */
+enum { VSR_EX_DOWN = 0, VSR_EX_INIT = 1, VSR_EX_UP = 2, VSR_EX_SEARCH = 3, VSR_EX_VOTE = 4 };
+int vsr_exemplar_run_stage(vsr_exemplar_t* h, uint8_t* frames_dev, int64_t frame_stride, int n, void* workspace, int64_t workspace_bytes,
+                           int stage, int level, int iteration, int pass, int from_b, void* stream);
+/* n frames uint8 [H][W][3] on the device, frame f at frames_dev + f * frame_stride bytes, masked pixels filled in place; every
+ * other byte stays.  workspace: device memory of at least vsr_exemplar_workspace_bytes(h, n), 4-byte aligned.
+ * The frames are READ at dword granularity: a source row is fetched as the aligned 4-byte words that hold its bytes, so up to 3
+ * bytes in front of a frame's first byte and behind its last one are read (never written), always inside a word that holds a byte
+ * of the frame.  Any device allocation satisfies this; frames_dev and frame_stride need no alignment. */
+int vsr_exemplar_inpaint(vsr_exemplar_t* h, uint8_t* frames_dev, int64_t frame_stride, int n, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Text detector: the operators of the PP-OCRv5 detection inference programs the reference
  * loads through paddleocr (backend/tools/subtitle_detect.py:41-58, backend/models/V5/{ch_det,ch_det_fast}/inference.json).
  * NCHW fp32 device tensors; the host runner (backend/tools/ocr_det.py) walks the program and calls one launcher per op.

@@ -16,6 +16,8 @@ BMODE_NK, BMODE_KN = 0, 1
 ACT_NONE, ACT_LRELU02 = 0, 1
 TILE_128x128, TILE_256x32, TILE_256x64, TILE_128x64 = 0, 1, 2, 3
 TILE_256x128, TILE_256x256 = 4, 5      # 8-wave tiles of the fp16-operand kernels (variant 6, NK)
+EX_DOWN, EX_INIT, EX_UP, EX_SEARCH, EX_VOTE = range(5)      # stages of vsr_exemplar_run_stage
+EX_INFO_LEN = 10
 TILE_DIMS = {TILE_128x128: (128, 128), TILE_256x32: (256, 32), TILE_256x64: (256, 64), TILE_128x64: (128, 64), TILE_256x128: (256, 128), TILE_256x256: (256, 256)}
 
 
@@ -226,6 +228,17 @@ SIGNATURES = {
     "vsr_telea_plan_tmap": (_I, [_P, _P]),
     "vsr_telea_plan_weights": (_I, [_P, _P, _P]),
     "vsr_telea_inpaint": (_I, [_P, _P, _L, _I, _P]),
+    "vsr_exemplar_create": (_I, [C.POINTER(_P), _I]),
+    "vsr_exemplar_destroy": (None, [_P]),
+    "vsr_exemplar_set_mask": (_I, [_P, _P, _I, _I]),
+    "vsr_exemplar_plan_levels": (_I, [_P]),
+    "vsr_exemplar_plan_level_info": (_I, [_P, _I, _P]),
+    "vsr_exemplar_plan_read": (_I, [_P, _I, _P, _P, _P, _P]),
+    "vsr_exemplar_plan_init": (_I, [_P, _P]),
+    "vsr_exemplar_workspace_bytes": (_L, [_P, _I]),
+    "vsr_exemplar_layout": (_I, [_P, _I, _I, _P]),
+    "vsr_exemplar_run_stage": (_I, [_P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "vsr_exemplar_inpaint": (_I, [_P, _P, _L, _I, _P, _L, _P]),
     "vsr_feather_alpha": (_I, [_P, _I, _I, _I, _P, _P]),
     "vsr_feather_composite": (_I, [_P, _L, _P, _L, _P, _I, _I, _I, _I, _P]),
     "vsr_regrain_sets": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),

@@ -9,17 +9,34 @@ OpenCV's Telea fill is restated (tests/_telea_statement.py): the fast
 the engine builds it once per mask on the host and replays it on every frame in a HIP kernel.  Parity with cv2 itself is
 pinned only where cv2 can be imported (tests/test_gpu_telea.py).  The reference's own pass-through survives as an explicit
 choice, VSR_OPENCV_BACKEND=cv2, honoured only where cv2 imports; the default is the GPU path everywhere and has no CPU path.
+
+--opencv-fill exemplar (VSR_OPENCV_FILL; default telea) swaps the fill itself: a PatchMatch exemplar fill, coarse to fine, that copies
+real texture from the picture around the hole (engine.ExemplarEngine, tests/_exemplar_statement.py).  Everything
+around the fill -- the plugin contract, composite_mask, sample_rows, the cosmetic passes of tools/seam_feather.py -- is the same.
 """
 import os
 
 import numpy as np
 import torch
 
-from ...engine import TeleaEngine
+from ...engine import ExemplarEngine, TeleaEngine
 from ..tools import seam_feather
 from .sttn_auto_inpaint import _device_index
 
 RADIUS = 3                                                                   # opencv_inpaint.py:9
+FILLS = ("telea", "exemplar")
+
+
+def fill_option(value=None):
+    """--opencv-fill / VSR_OPENCV_FILL -> "telea" or "exemplar"; None reads the environment, unset or empty is telea.  ValueError otherwise."""
+    if value is None:
+        value = os.environ.get("VSR_OPENCV_FILL", "")
+    text = str(value).strip().lower()
+    if text == "":
+        return "telea"
+    if text not in FILLS:
+        raise ValueError(f"the opencv fill must be one of {', '.join(FILLS)}, not {value!r}")
+    return text
 
 
 def available():
@@ -41,10 +58,22 @@ def _mask2d(mask):
 class OpenCVInpaint:
     accepts_device_frames = True      # __call__ also takes a uint8 [n,H,W,3] device tensor and inpaints it in place (tools/resident.py)
 
-    def __init__(self, device="cuda:0", engine=None):
+    def __init__(self, device="cuda:0", engine=None, fill=None):
         self.device = device
         self._cv2 = None
-        if engine is None and os.environ.get("VSR_OPENCV_BACKEND", "").lower() == "cv2" and available():
+        if engine is not None:
+            # a passed engine is the fill: the option is not read, and an explicit `fill` that names the other one is refused
+            self.fill = "exemplar" if isinstance(engine, ExemplarEngine) else "telea"
+            if fill is not None and fill_option(fill) != self.fill:
+                raise ValueError(f"fill={fill!r} does not match the engine that was passed, which fills by {self.fill}")
+        else:
+            self.fill = fill_option(fill)
+        wants_cv2 = os.environ.get("VSR_OPENCV_BACKEND", "").lower() == "cv2"
+        if self.fill == "exemplar" and engine is None:
+            if wants_cv2:
+                raise ValueError("VSR_OPENCV_BACKEND=cv2 hands the fill to cv2.inpaint, which has no exemplar fill: drop one of the two")
+            self.engine = ExemplarEngine(device=_device_index(device))
+        elif engine is None and wants_cv2 and available():
             import cv2
 
             self._cv2 = cv2
@@ -55,7 +84,7 @@ class OpenCVInpaint:
 
     def clone(self):
         """a second instance on the same device: its own engine and plan cache (tools/batch_lanes.py)"""
-        return OpenCVInpaint(self.device)
+        return OpenCVInpaint(self.device, fill=self.fill)
 
     def close(self):
         if self.engine is not None:

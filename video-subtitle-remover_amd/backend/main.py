@@ -708,7 +708,7 @@ FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDE
             ("sttn_lookahead", "VSR_STTN_LOOKAHEAD", str), ("seam_feather", "VSR_SEAM_FEATHER", str), ("regrain", "VSR_REGRAIN", str),
             ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str),
             ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str), ("borrow", "VSR_BORROW", str),
-            ("borrow_pan", "VSR_BORROW_PAN", str),
+            ("borrow_pan", "VSR_BORROW_PAN", str), ("opencv_fill", "VSR_OPENCV_FILL", str),
             ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"), ("logo_unblend", "VSR_LOGO_UNBLEND", lambda _: "1"))
 
 

@@ -86,12 +86,26 @@ def build_parser():
                              "estimated from the frames the scan sampled, and every frame's area gets (I - a L) / (1 - a) of its "
                              "source; the fill stays under the opaque part, and an area whose overlay is opaque, too faint, in a "
                              "still shot or crossed by a text box is inpainted as before; sets VSR_LOGO_UNBLEND=1")
+    # not in the reference: opencv mode's fill itself (inpaint/opencv_inpaint.py)
+    parser.add_argument("--opencv-fill", type=str, default=None, metavar="{telea,exemplar}",
+                        help="--inpaint-mode opencv: telea = OpenCV's Telea fill (default), exemplar = a PatchMatch exemplar fill, coarse to "
+                             "fine, that copies real texture from the picture around the hole instead of diffusing the rim inwards; needs "
+                             "no weights; sets VSR_OPENCV_FILL")
     return parser
 
 
 def parse_args(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.opencv_fill is not None:
+        from ..inpaint.opencv_inpaint import fill_option
+
+        try:
+            args.opencv_fill = fill_option(args.opencv_fill)
+        except ValueError as e:
+            parser.error(f"--opencv-fill: {e}")
+        if args.opencv_fill == "exemplar" and args.inpaint_mode != "opencv":
+            parser.error("--opencv-fill exemplar: it is the fill of --inpaint-mode opencv, and the mode is " + args.inpaint_mode)
     if args.seam_feather is not None:
         from .seam_feather import feather_option
 

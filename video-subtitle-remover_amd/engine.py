@@ -988,3 +988,150 @@ class TeleaEngine:
         with torch.cuda.device(frames.device):
             check(lib.vsr_telea_inpaint(h, C.c_void_p(frames.data_ptr()), stride, n, _stream_ptr()))
         return frames
+
+
+class ExemplarEngine:
+    """--opencv-fill exemplar: a PatchMatch exemplar fill, coarse to fine, in place of Telea's diffusion (the statement
+    is tests/_exemplar_statement.py).  Pyramid sizes, valid sources, targets, tiles and the coarsest level's interpolation offsets depend
+    on the mask alone: they are built once per mask on the host (csrc/exemplar_plan.cpp) and all frames of a call run the kernels of
+    csrc/exemplar_kernels.hip together.  The plans of the last `max_plans` masks are kept, keyed by the mask's bytes, as TeleaEngine
+    keeps its own; the workspace is a torch tensor kept per (n, plan, stream): a call's launches use it in the order of the stream
+    that is current at the call, so two streams never share one, and a tensor that is dropped goes back to the allocator, which hands
+    its memory out again only behind the work of the stream it was allocated on."""
+
+    def __init__(self, device=0, max_plans=4):
+        if device is not None and device >= 0:
+            require_gpu()
+        self.device_index = -1 if device is None else int(device)
+        self.device = torch.device("cuda", self.device_index) if self.device_index >= 0 else torch.device("cpu")
+        self.max_plans = int(max_plans)
+        self._plans = {}                 # (H, W, mask bytes) -> handle; insertion order = least recently used first
+        self._workspaces = {}            # (n, handle value, stream) -> uint8 tensor
+        self.plan_builds = 0
+        self.plan_hits = 0
+        h = C.c_void_p()                 # arguments are checked now, not at the first mask
+        check(lib.vsr_exemplar_create(C.byref(h), self.device_index))
+        lib.vsr_exemplar_destroy(h)
+
+    def close(self):
+        for h in getattr(self, "_plans", {}).values():
+            lib.vsr_exemplar_destroy(h)
+        self._plans = {}
+        self._workspaces = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _drop(self, h):
+        lib.vsr_exemplar_destroy(h)                                              # synchronises the device before freeing
+        self._workspaces = {k: w for k, w in self._workspaces.items() if k[1] != h.value}
+
+    def plan(self, mask):
+        """the handle holding `mask`'s plan (host uint8 [H,W], non-zero = fill): cached, or built and uploaded now.  A mask that leaves
+        nothing to copy from is refused here (VsrError), before any frame is touched."""
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert mask.ndim == 2, "mask must be [H, W]"
+        key = (mask.shape[0], mask.shape[1], mask.tobytes())
+        h = self._plans.pop(key, None)
+        if h is None:
+            h = C.c_void_p()
+            check(lib.vsr_exemplar_create(C.byref(h), self.device_index))
+            try:
+                if self.device_index >= 0:
+                    with torch.cuda.device(self.device):
+                        check(lib.vsr_exemplar_set_mask(h, mask.ctypes.data_as(C.c_void_p), mask.shape[0], mask.shape[1]))
+                else:
+                    check(lib.vsr_exemplar_set_mask(h, mask.ctypes.data_as(C.c_void_p), mask.shape[0], mask.shape[1]))
+            except Exception:
+                lib.vsr_exemplar_destroy(h)
+                raise
+            self.plan_builds += 1
+            while len(self._plans) >= self.max_plans:
+                self._drop(self._plans.pop(next(iter(self._plans))))
+        else:
+            self.plan_hits += 1
+        self._plans[key] = h
+        return h
+
+    def plan_levels(self, mask):
+        """per level (finest first) a dict of H, W, S, D (int16 [.,2]), tiles (int32 [.,2]), cls (uint8 [H,W]) and box (y0, x0, h, w)"""
+        h = self.plan(mask)
+        out = []
+        for l in range(lib.vsr_exemplar_plan_levels(h)):
+            info = np.zeros(_lib.EX_INFO_LEN, np.int64)
+            check(lib.vsr_exemplar_plan_level_info(h, l, info.ctypes.data_as(C.c_void_p)))
+            H, W, ns, nt, ntiles, nhole = (int(v) for v in info[:6])
+            S, D = np.zeros((ns, 2), np.int16), np.zeros((nt, 2), np.int16)
+            tiles, cls = np.zeros((ntiles, 2), np.int32), np.zeros((H, W), np.uint8)
+            check(lib.vsr_exemplar_plan_read(h, l, *(a.ctypes.data_as(C.c_void_p) for a in (S, D, tiles, cls))))
+            out.append(dict(H=H, W=W, S=S, D=D, tiles=tiles, cls=cls, holes=nhole, box=tuple(int(v) for v in info[6:10])))
+        return out
+
+    def plan_init(self, mask):
+        """the coarsest level's interpolation table, int32 [its hole pixels, 6]"""
+        h = self.plan(mask)
+        levels = self.plan_levels(mask)
+        table = np.zeros((levels[-1]["holes"] if levels else 0, 6), np.int32)
+        if table.size:
+            check(lib.vsr_exemplar_plan_init(h, table.ctypes.data_as(C.c_void_p)))
+        return table
+
+    def layout(self, mask, n, level):
+        """(image offset or -1, bytes per image, field A offset, field B offset, bytes per frame of a field) in the workspace of n frames"""
+        out = np.zeros(5, np.int64)
+        check(lib.vsr_exemplar_layout(self.plan(mask), n, level, out.ctypes.data_as(C.c_void_p)))
+        return tuple(int(v) for v in out)
+
+    def workspace(self, h, n):
+        """the workspace of a call of n frames under this plan on the current stream (allocated on it at first use)"""
+        key = (n, h.value, torch.cuda.current_stream(self.device).cuda_stream)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            size = int(lib.vsr_exemplar_workspace_bytes(h, n))
+            assert size >= 0
+            while len(self._workspaces) >= self.max_plans:                       # a clip's last, shorter batch must not pile up tensors
+                self._workspaces.pop(next(iter(self._workspaces)))
+            ws = torch.empty(max(size, 4), dtype=torch.uint8, device=self.device)
+            self._workspaces[key] = ws
+        return ws
+
+    @staticmethod
+    def _frames_args(frames):
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 4 and frames.shape[3] == 3
+        n, H, W, _ = frames.shape
+        assert frames.stride(3) == 1 and frames.stride(2) == 3 and frames.stride(1) == 3 * W, "frames must be contiguous [H,W,3]"
+        return n, H, W, (frames.stride(0) if n > 1 else H * W * 3)
+
+    def run_stage(self, frames, mask, stage, level, iteration=0, pass_=0, from_b=False):
+        """one launch (the per-launch tests and scripts/bench_exemplar.py): stage is one of _lib.EX_*; returns the workspace tensor"""
+        n, H, W, stride = self._frames_args(frames)
+        h = self.plan(mask)
+        ws = self.workspace(h, n)
+        with torch.cuda.device(frames.device):
+            check(lib.vsr_exemplar_run_stage(h, C.c_void_p(frames.data_ptr()), stride, n, C.c_void_p(ws.data_ptr()), ws.numel(), int(stage),
+                                             int(level), int(iteration), int(pass_), int(bool(from_b)), _stream_ptr()))
+        return ws
+
+    def inpaint(self, frames, mask, out=None):
+        """frames uint8 [n,H,W,3] on the GPU (each frame contiguous), mask HOST uint8 [H,W] (numpy; non-zero = fill).  out=None
+        or out=frames: in place; another tensor: the frames are copied there first and filled there.  Returns the filled tensor."""
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 4 and frames.shape[3] == 3
+        n, H, W, _ = frames.shape
+        if isinstance(mask, torch.Tensor):
+            mask = mask.cpu().numpy()
+        assert tuple(mask.shape) == (H, W), f"mask {tuple(mask.shape)} does not fit frames {(H, W)}"
+        h = self.plan(mask)                                                      # refuses before a frame is touched
+        if out is not None and out.data_ptr() != frames.data_ptr():
+            assert out.shape == frames.shape and out.dtype == torch.uint8 and out.device == frames.device
+            out.copy_(frames)
+            frames = out
+        if n == 0:
+            return frames
+        n, H, W, stride = self._frames_args(frames)
+        ws = self.workspace(h, n)
+        with torch.cuda.device(frames.device):
+            check(lib.vsr_exemplar_inpaint(h, C.c_void_p(frames.data_ptr()), stride, n, C.c_void_p(ws.data_ptr()), ws.numel(), _stream_ptr()))
+        return frames
