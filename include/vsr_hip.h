@@ -888,6 +888,29 @@ int vsr_static_classify(const uint8_t* lo_dev, const uint8_t* hi_dev, const uint
                         float* grown_dev, uint8_t* moving_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Stroke-like text (--text-detect strokes, csrc/stroke_kernels.hip; the statement is tests/_strokes_statement.py, the design DESIGN.md
+ * 4.22): the device part of a text detector that needs no weights -- thin bright or dark strokes with strong contrast, in both
+ * orientations, packed densely along a line.  Integer, bit-exact; all pointers are device pointers, all work is issued on `stream`,
+ * nothing waits for the device.  backend/tools/stroke_det.py labels every frame's text map with vsr_det_launch_ccl and chooses the boxes
+ * on the host.  Bad arguments (a null pointer, H, W or n <= 0, n above 65535, H * W * 3 >= 2^31, F outside 1..8 or larger than H or W, S
+ * outside 1..8, C outside 1..255, a stride smaller than a frame; hc or wc <= 0, hc * wc >= 2^31 / 5, WX or WY outside 0..8, NV or NH
+ * outside 0..65535, a misaligned text map) return VSR_ERR_ARG and launch nothing.
+ * ------------------------------------------------------------------------------------- */
+/* ONE launch over the n frames frames_dev + k * frame_stride (uint8 [H][W][3] BGR each).  Per frame the analysis picture y [h][w], h = H /
+ * F, w = W / F: y = (the sum of the F x F lumas Y = (29 B + 150 G + 77 R + 128) >> 8 + F F / 2) / (F F); rows and columns beyond h F, w F
+ * are not read.  With the indices clamped to the analysis picture, a pixel is a V-stroke pixel when y - max(loL, loR) >= C or min(hiL,
+ * hiR) - y >= C, lo / hi the minimum / maximum of the S pixels to its left (L) and right (R), and an H-stroke pixel by the same test
+ * over the S pixels above and below.  cv_dev, ch_dev uint8 [n][hc][wc], hc = ceil(h / 4), wc = ceil(w / 4): the V- and H-stroke pixels
+ * of every 4 x 4 cell (0..16; pixels outside the analysis picture count 0). */
+int vsr_strokes_cells(const uint8_t* frames_dev, int64_t frame_stride, int n, int H, int W, int F, int S, int C, uint8_t* cv_dev, uint8_t* ch_dev,
+                      void* stream);
+/* ONE launch on the planes of vsr_strokes_cells: text_dev float [n][hc][wc] = 1.0 where the sum of cv over the (2 WX + 1) x (2 WY + 1)
+ * cells centred on the cell is at least NV and that of ch at least NH (cells outside the plane count 0), else 0.0 -- the map
+ * vsr_det_launch_ccl labels at threshold 0.5, one call per frame. */
+int vsr_strokes_text(const uint8_t* cv_dev, const uint8_t* ch_dev, int n, int hc, int wc, int WX, int WY, int NV, int NH, float* text_dev,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Un-mixing translucent overlays (--logo-unblend, csrc/unmix_kernels.hip; the statement is tests/_unmix_statement.py, the design
  * DESIGN.md 4.20): an overlay I = (1 - a) B + a L that --logo-scan found gives the picture back as B = (I - o) / g.  Integer, bit-exact;
  * all pointers but `box` are device pointers, all work is issued on `stream`, nothing waits for the device.  backend/tools/unblend.py

@@ -262,6 +262,8 @@ SIGNATURES = {
     "vsr_static_classify": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vsr_unmix_accum": (_I, [_P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "vsr_unmix_apply": (_I, [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vsr_strokes_cells": (_I, [_P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "vsr_strokes_text": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vsr_plan_consts": (_L, [_P, _P, _L]),
     "vsr_plan_destroy": (None, [_P]),
     "vsr_plan_num_buffers": (_I, [_P]),
@@ -283,6 +285,10 @@ SIGNATURES = {
     "vsr_flow_timing_get": (_I, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "vsr_flow_timing_keys": (C.c_int64, [_P, C.c_int64]),
 }
+# symbols of an opt-in path that are looked up on their first use (lazy()), not when the library is loaded: with the option off, none
+# of them is touched
+LAZY = frozenset(("vsr_strokes_cells", "vsr_strokes_text"))
+lazy_bound = set()                     # the names lazy() has looked up in this process
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -300,9 +306,20 @@ from . import switches  # noqa: E402
 switches.export_defaults()             # the library reads some switches itself, once per process (switches.py)
 lib = C.CDLL(LIB_PATH)
 for _name, (_res, _args) in SIGNATURES.items():
+    if _name in LAZY:
+        continue
     _fn = getattr(lib, _name)          # AttributeError here = library does not match the header
     _fn.restype = _res
     _fn.argtypes = _args
+
+
+def lazy(name):
+    """the function `name` of LAZY with its signature set, looked up in the library on the first call"""
+    fn = getattr(lib, name)            # AttributeError here = library does not match the header
+    if name not in lazy_bound:
+        fn.restype, fn.argtypes = SIGNATURES[name]
+        lazy_bound.add(name)
+    return fn
 
 
 def last_error():

@@ -614,6 +614,12 @@ class SubtitleRemover:
         """the injected detector if any, else the MI355X TextDetection configured through the environment (tools/ocr_det.py)"""
         det = getattr(self, "text_detector", None)
         if det is None:
+            from .tools import stroke_det
+
+            if stroke_det.detect_option() == "strokes":                  # --text-detect strokes: no weights (tools/stroke_det.py)
+                if getattr(self, "_stroke_detector", None) is None:
+                    self._stroke_detector = stroke_det.StrokeTextDetection(self._device_index())
+                return self._stroke_detector
             from .tools import ocr_det
 
             det = ocr_det.from_env(self._device_index())
@@ -630,6 +636,11 @@ class SubtitleRemover:
         from .tools import unblend
 
         unmix = unblend.refuse()                             # --logo-unblend: a bad value, or on without --logo-scan, likewise
+        from .tools import stroke_det
+
+        if stroke_det.detect_option() == "strokes":          # --text-detect: a bad value; strokes in a mode without a detector, beside an injected one, or on several ranks, likewise
+            stroke_det.refuse(self._distributed(), self.is_picture or config.inpaintMode.value != InpaintMode.STTN_AUTO,
+                              getattr(self, "text_detector", None))
         try:
             self._run(scan, unmix, start_time)
         finally:
@@ -709,7 +720,8 @@ FLAG_ENV = (("y4m_out", "VSR_Y4M_OUT", str), ("resident_windows", "VSR_IO_RESIDE
             ("deflicker", "VSR_DEFLICKER", str), ("tone_match", "VSR_TONE_MATCH", str),
             ("glyph_key", "VSR_GLYPH_KEY", str), ("glyph_hold", "VSR_GLYPH_HOLD", str), ("borrow", "VSR_BORROW", str),
             ("borrow_pan", "VSR_BORROW_PAN", str), ("opencv_fill", "VSR_OPENCV_FILL", str),
-            ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"), ("logo_unblend", "VSR_LOGO_UNBLEND", lambda _: "1"))
+            ("logo_scan", "VSR_LOGO_SCAN", lambda _: "1"), ("logo_unblend", "VSR_LOGO_UNBLEND", lambda _: "1"),
+            ("text_detect", "VSR_TEXT_DETECT", str))
 
 
 def main(argv=None):

@@ -91,6 +91,14 @@ def build_parser():
                         help="--inpaint-mode opencv: telea = OpenCV's Telea fill (default), exemplar = a PatchMatch exemplar fill, coarse to "
                              "fine, that copies real texture from the picture around the hole instead of diffusing the rim inwards; needs "
                              "no weights; sets VSR_OPENCV_FILL")
+    # not in the reference: which text detector the detector-driven modes use (tools/stroke_det.py)
+    parser.add_argument("--text-detect", type=str, default=None, metavar="{model,strokes}",
+                        help="the text detector of sttn-det, lama, propainter, opencv and picture mode: model = the PP-OCRv5 network "
+                             "(default; needs VSR_DET_MODEL_DIR and its weights), strokes = a weight-free detector on the GPU of "
+                             "stroke-like text (thin bright or dark strokes with strong contrast, both ways, dense along a line: a "
+                             "burnt-in subtitle with an outline or a shadow); it misses text without contrast, strokes wider than 6 "
+                             "analysis pixels, a single very short word and vertical text, and takes dense fine texture for text; one "
+                             "process; sets VSR_TEXT_DETECT")
     return parser
 
 
@@ -106,6 +114,13 @@ def parse_args(argv=None):
             parser.error(f"--opencv-fill: {e}")
         if args.opencv_fill == "exemplar" and args.inpaint_mode != "opencv":
             parser.error("--opencv-fill exemplar: it is the fill of --inpaint-mode opencv, and the mode is " + args.inpaint_mode)
+    if args.text_detect is not None:
+        from .stroke_det import detect_option
+
+        try:
+            args.text_detect = detect_option(args.text_detect)
+        except ValueError as e:
+            parser.error(f"--text-detect: {e}")               # (strokes with sttn-auto is refused by the run, which knows a picture from a video)
     if args.seam_feather is not None:
         from .seam_feather import feather_option
 
