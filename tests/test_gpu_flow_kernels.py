@@ -45,6 +45,9 @@ PROTOTYPES = {
     "vsr_rfc_launch_deform_cols": "pppifiiiiipp",
     "vsr_rfc_launch_combine": "pipppiiippp",
     # pp_kernels.h
+    "vsr_pp_launch_mask_f32": "plpp",
+    "vsr_pp_launch_mask_u8": "plpp",
+    "vsr_pp_launch_imgprop": "ppppppiiiippp",
     "vsr_pp_launch_im2col3": "pppiiipp",
     "vsr_pp_launch_ds_flow": "piiipp",
     "vsr_pp_launch_ds_mask": "ppiiipiip",
@@ -1108,3 +1111,142 @@ def test_pp_small_kernels(K):
     launch(K.vsr_pp_launch_tanh_out, ptr(dev(y)), ld, n, H, W, ptr(to))
     ref = np.tanh(y[:, :3].astype(np.float64)).reshape(n, H, W, 3).transpose(0, 3, 1, 2)
     check("tanh_out", np.abs(to.cpu().numpy().reshape(n, 3, H, W) - ref).max(), 4 * U32)
+
+
+# =====================================================================================================================================
+# ProPainter image propagation (pp_kernels.hip: k_pp_imgprop, k_pp_mask_f32, k_pp_mask_u8) against tests/_pp_glue_ref.py, the numpy
+# restatement of propagate() that tests/test_pp_glue_reference.py holds against the torch oracle bit for bit
+# =====================================================================================================================================
+def _imgprop_launch(K, inp, first):
+    """one launch into sentinel-filled outputs with 64 floats behind each, which must keep the sentinel"""
+    Cc, h, w = inp["cur"].shape
+    prop, mprop = sent(Cc * h * w, extra=64), sent(h * w, extra=64)
+    launch(K.vsr_pp_launch_imgprop, ptr(dev(inp["prev_prop"])), ptr(dev(inp["prev_mask"])), ptr(dev(inp["cur"])), ptr(dev(inp["mcur"])),
+           ptr(dev(inp["fprop"])), ptr(dev(inp["fcheck"])), Cc, h, w, first, ptr(prop), ptr(mprop))
+    gp, gm = prop.cpu().numpy(), mprop.cpu().numpy()
+    untouched(gp[Cc * h * w:], np.ones(64, bool), "imgprop prop tail")
+    untouched(gm[h * w:], np.ones(64, bool), "imgprop mprop tail")
+    return gp[:Cc * h * w].reshape(Cc, h, w), gm[:h * w].reshape(h, w)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cc", [3, 1])
+@pytest.mark.parametrize("h,w", [(9, 17), (17, 33), (2, 9)])
+def test_imgprop_dyadic_grid_exact(K, h, w, Cc):
+    """h - 1 and w - 1 are powers of two and the flows multiples of 1/4: x + f, 2 pos / (size - 1), the un-normalisation and the
+    bilinear weights (multiples of 1/4, products multiples of 1/16, on check flows that are multiples of 1/4) are exact in fp32, so
+    every sampling position, tie included, is the float64 one and there is no margin: prop and mprop equal the restatement bit for
+    bit.  step_conditions asserts the shares of ties (>= 20 %, on even and odd lower neighbours), of nearest targets and bilinear
+    footprints outside the picture (>= 5 %, every side), of the eight (mcur, valid, mvalid) combinations and of the union branch
+    (some of it on targets outside the picture: the zero padding of the nearest warp), and that no forward-backward or mask decision is within fp32 rounding of its threshold (2x9: what 18 pixels can hold)."""
+    import _pp_glue_ref as R
+
+    inp = R.imgprop_inputs(R.step_seed(h, w), h, w, Cc, 0.0)
+    prop, mprop, info, _ = R.step_conditions(inp, True)
+    gp, gm = _imgprop_launch(K, inp, 0)
+    dp, dm = int((gp != prop).any(0).sum()), int((gm != mprop).sum())
+    print(f"imgprop dyadic {h}x{w} C={Cc}: {dp} pixels and {dm} mask cells differ (bound 0)")
+    assert dp == 0 and dm == 0
+
+
+def _imgprop_general_check(inp, gp, gm, prop, mprop, info, und, what):
+    """bit equality on decided pixels; an undecided pixel holds one of its candidates: cur or the propagated picture at one of the
+    four integer positions around the sampling position (zero outside), mask 0 or 1"""
+    import _pp_glue_ref as R
+
+    dec = ~und
+    dp, dm = int(((gp != prop).any(0) & dec).sum()), int(((gm != mprop) & dec).sum())
+    print(f"{what}: {dp} decided pixels and {dm} decided mask cells differ (bound 0); undecided {und.mean():.5f} (cap 0.005)")
+    assert dp == 0 and dm == 0
+    y0, x0 = np.floor(info["iy"]).astype(np.int64), np.floor(info["ix"]).astype(np.int64)
+    cands = [inp["cur"]] + [R.gather(inp["prev_prop"], y0 + dy, x0 + dx) for dy in (0, 1) for dx in (0, 1)]
+    anyc = np.any([gp == c for c in cands], axis=0).all(0)
+    assert anyc[und].all() and np.isin(gm[und], (0.0, 1.0)).all(), "an undecided pixel holds none of its candidates"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Cc", [3, 1])
+@pytest.mark.parametrize("h,w", [(13, 22), (45, 75), (2, 3)])
+def test_imgprop_general_grid(K, h, w, Cc):
+    """Sizes whose positions round in fp32 (2x3: size - 1 = 1, the normalisation's max(size - 1, 1)), flows with N(0, 0.2) on top of
+    the blocks.  A pixel is undecided where a float64 margin (forward-backward test, warped mask against 0.1, nearest position
+    against a .5 tie) is below what fp32 can move it by -- R.imgprop_bounds derives it from u = 2^-24 and the magnitudes involved;
+    step_conditions caps their share at 0.5 % (these inputs: 0 to 6e-4) and asserts the branch shares as on the dyadic grid."""
+    import _pp_glue_ref as R
+
+    inp = R.imgprop_inputs(R.step_seed(h, w), h, w, Cc, 0.2)
+    prop, mprop, info, und = R.step_conditions(inp, False)
+    gp, gm = _imgprop_launch(K, inp, 0)
+    _imgprop_general_check(inp, gp, gm, prop, mprop, info, und, f"imgprop general {h}x{w} C={Cc}")
+
+
+@pytest.mark.gpu
+def test_imgprop_second_turn_of_the_stride_loop(K):
+    """h w = 1449 x 1448 = 2 097 152 + 1000 pixels: the grid is capped at 8192 blocks of 256 threads, so 1000 threads take a
+    second pixel (1080p stays below the cap).  fp32 positions are 1e-4 wide at x = 1448, so this case keeps the check flow free of
+    per-pixel noise and sends no block a picture's width away: 0.42 % of its pixels are undecided (cap 0.5 %)"""
+    import _pp_glue_ref as R
+
+    h, w = R.LARGE_SIZE
+    assert h * w == 8192 * 256 + 1000
+    inp = R.imgprop_inputs(R.step_seed(h, w), h, w, 3, 0.2, far=False, bad=0.1, check_noise=False)
+    prop, mprop, info, und = R.step_conditions(inp, False, oob=False)
+    gp, gm = _imgprop_launch(K, inp, 0)
+    _imgprop_general_check(inp, gp, gm, prop, mprop, info, und, f"imgprop {h}x{w}")
+    sel = ~und[-1, -1000:]                              # the pixels of the second turn: the union branch is taken among them too
+    assert sel.sum() > 900 and (info["union"][-1, -1000:][sel] == 1).any()
+    assert np.array_equal(gp[:, -1, -1000:][:, sel], prop[:, -1, -1000:][:, sel]) and np.array_equal(gm[-1, -1000:][sel], mprop[-1, -1000:][sel])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,w,Cc", [(9, 17, 3), (45, 75, 1)])
+def test_imgprop_first_step_copies(K, h, w, Cc):
+    """first = 1: prop and mprop are copies of cur and mcur; the propagated picture, its mask and both flows are NaN and none of it
+    reaches the output"""
+    import _pp_glue_ref as R
+
+    inp = R.imgprop_inputs(R.step_seed(h, w), h, w, Cc, 0.0)
+    inp = {k: (v if k in ("cur", "mcur") else np.full_like(v, np.nan)) for k, v in inp.items()}
+    gp, gm = _imgprop_launch(K, inp, 1)
+    assert np.array_equal(gp.view(np.uint32), inp["cur"].view(np.uint32)) and np.array_equal(gm.view(np.uint32), inp["mcur"].view(np.uint32))
+
+
+MASK_N = (1, 255, 257, 8192 * 256 + 77)               # below / above one block, and the second turn of the capped grid
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", MASK_N)
+def test_pp_mask_f32(K, n):
+    """u8 -> fp32 {0, 1}: any non-zero byte is a hole; from n = 257 on all 256 byte values occur"""
+    src = ((np.arange(n, dtype=np.int64) * 37 + 255) % 256).astype(np.uint8)
+    assert n < 256 or len(np.unique(src)) == 256
+    out = sent(n, extra=64)
+    launch(K.vsr_pp_launch_mask_f32, ptr(dev(src)), n, ptr(out))
+    got = out.cpu().numpy()
+    assert np.array_equal(got[:n], (src != 0).astype(np.float32)) and set(np.unique(got[:n])) <= {0.0, 1.0}
+    untouched(got[n:], np.ones(64, bool), "mask_f32 tail")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", MASK_N)
+def test_pp_mask_u8(K, n):
+    """fp32 -> u8: 1 where the value exceeds 0.5 -- 0.5 itself, its lower neighbour, 0, -0.0, 0.1 and NaN give 0; the upper
+    neighbour of 0.5 and 1 give 1"""
+    half = np.float32(0.5)
+    special = np.array([half, np.nextafter(half, np.float32(1)), np.nextafter(half, np.float32(0)), 0.0, 1.0, -0.0, 0.1, np.nan], dtype=np.float32)
+    want8 = np.array([0, 1, 0, 0, 1, 0, 0, 0], dtype=np.uint8)
+    idx = (np.arange(n) * 3 + 1) % 8                   # n = 1: the upper neighbour of 0.5
+    out = torch.full((n + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+    launch(K.vsr_pp_launch_mask_u8, ptr(dev(special[idx])), n, ptr(out))
+    got = out.cpu().numpy()
+    assert np.array_equal(got[:n], want8[idx])
+    assert np.all(got[n:] == 0xA5), "mask_u8 wrote behind its n bytes"
+
+
+@pytest.mark.gpu
+def test_pp_mask_empty(K):
+    """n = 0: both launchers return 0 and write nothing"""
+    f, b = sent(64), torch.full((64,), 0xA5, dtype=torch.uint8, device="cuda")
+    launch(K.vsr_pp_launch_mask_f32, ptr(b), 0, ptr(f))
+    launch(K.vsr_pp_launch_mask_u8, ptr(f), 0, ptr(b))
+    assert np.all(f.cpu().numpy() == SENT) and np.all(b.cpu().numpy() == 0xA5)

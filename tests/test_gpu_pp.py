@@ -36,6 +36,28 @@ def test_image_propagation_bit_exact(engine, gpu_device, t, H, W):
     assert mism <= 1e-4 and diff <= 1e-4
 
 
+@pytest.mark.parametrize("t", [4, 1])
+def test_image_propagation_dyadic_grid_exact(engine, gpu_device, t):
+    """17 x 33 (h - 1 and w - 1 powers of two) with flows that are multiples of 1/4, constant on 3x3 blocks: every sampling
+    position, bilinear weight and warped check flow is exact in fp32, so no thresholded decision can flip on a last bit and the
+    allowance of the test above has nothing to cover: zero mismatches.  Each frame has its own mask and picture and each flow its
+    own blocks, so a wrong frame, flow or role index in either direction of the plan (pp_plan.cpp) shows; t = 1 is two first
+    steps.  tests/test_pp_glue_reference.py holds the same clip against the float32 and float64 restatements on the CPU."""
+    from _pp_glue_ref import imgprop_clip
+
+    masked, masks, ff, fb = imgprop_clip(70 + t, t, 17, 33)
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(gpu_device)
+    got, gm = engine.img_propagation(d(masked), d(ff), d(fb), d(masks[:, 0].astype(np.uint8)))
+    torch.cuda.synchronize()
+    ref, rm = ProPainterOracle({}).img_propagation(torch.from_numpy(masked), torch.from_numpy(ff), torch.from_numpy(fb),
+                                                   torch.from_numpy(masks).clone())
+    mism = int((gm.cpu().numpy() != rm[:, 0].numpy().astype(np.uint8)).sum())
+    diff = int((got.cpu() != ref).sum().item())
+    print(f"imgprop dyadic clip t={t} 17x33: {mism} mask mismatches, {diff} pixel mismatches (bound 0), "
+          f"filled {1 - rm.sum().item() / masks.sum():.3f}")
+    assert mism == 0 and diff == 0
+
+
 @pytest.fixture(scope="module")
 def pp_sd():
     from vsr_amd.synth import make_propainter_state_dict
